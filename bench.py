@@ -40,6 +40,14 @@ PNG / .flo files) on a small synthetic KITTI-shaped set at 64 x 384 x 1280 - a s
 `hbm_reference`: what a plain device copy / read-only reduction reaches on this box.
 `cpu_baseline`: the CPU oracle (our plain-C restatement of the reference algorithm, OpenMP) timed on this host on a
 bounded sample of the same workload (dynamic pairs), rank 0, N=1 only.
+
+A plain run sets up, warms up, times the `--steps` steps and prints the line: `value`, `ms_per_step`, `config` and the headline
+`roofline` (from the HIP events of the timed launches).  Every record that takes runs of its own - `host_prep_comparison`, `batch512`,
+`sub`, `overlap`, `hbm_reference`, `roofline_n1`, the generator records and `cpu_baseline` - is measured only with `--full`
+(`--no-sub`, `--no-generator`, `--no-cpu-baseline` still leave parts of it out).
+`--dump-outputs DIR` (rank 0): after the timed steps, what the timed path handed back for the last pairs of its last step - per pair the
+merged flow, frame and fill mask and the moving-object chain's results - as DIR/<name>.npy in float32 (int64 as float64; a fixed,
+seeded sample of every array's elements when all of them together would exceed 64 MB).  Inputs and poses are seeded: the same arguments give the same inputs.
 """
 import argparse
 import ctypes
@@ -113,6 +121,11 @@ def parse():
                    help="run on libmpiflow_hip_witness.so (the -DMPF_WITNESS build: retired kernel variants and timing ablations, --tune ovl_xcd_a / view_shift / "
                         "ovl_ablate / stage_b ...); recorded in config.library - a line measured on it is not the product's")
     p.add_argument("--single-view-launches", action="store_true", help="tuning: one Stage B launch per view instead of one per pair")
+    p.add_argument("--full", action="store_true",
+                   help="also measure the records that take runs of their own: host-prep comparison, batch512, sub-records, overlap, HBM reference, "
+                        "N1 roofline, generator records, CPU baseline (a plain run times the headline only)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the timed path computed for the last pairs of its last step as DIR/<name>.npy (float32, at most 64 MB)")
     return p.parse_args()
 
 
@@ -426,6 +439,56 @@ def hbm_reference(dev, nbytes=1 << 30, reps=10):
     return rec
 
 
+DUMP_BYTES = 60 * 10 ** 6   # --dump-outputs: most bytes of array data written in all (the .npy headers stay within 64 MB beside it)
+
+
+def _chain_outputs(out, prefix, b):
+    """The moving-object chain's results of one pair (ops.MovingObjectBuffers) into `out`."""
+    out.update({prefix + k: v for k, v in (("chain_p1", b.p1), ("chain_z1", b.z1), ("chain_safe_x", b.safe_x), ("chain_safe_y", b.safe_y),
+                                           ("chain_flow_01", b.flow_01), ("chain_warped", b.warped))})
+    out.update({prefix + "chain_mask_" + k.replace("'", "p"): v for k, v in b.masks.items()})
+
+
+def last_step_outputs(wl, pairs_last_step):
+    """What the timed path handed its caller for the last pairs of its last step that are still resident: the pipelined workload's three
+    alternating output sets (p0 = the last pair, p1 the one before, ...), the serial workload's one.  -> {name: device tensor}"""
+    out = {}
+    if isinstance(wl, PipelinedWorkload):
+        n = wl.n_pushed
+        for j in range(min(len(wl.mix), pairs_last_step, n)):
+            k = n - 1 - j                       # push() index of the pair: its outputs went to mix[k % 3], its chain's to the chain's set k % n_buffers
+            flow, frame, fill = wl.mix[k % len(wl.mix)]
+            out.update({"p%d_flow_mix" % j: flow, "p%d_frame_mix" % j: frame, "p%d_fill_mask" % j: fill})
+            if wl.mo is not None:
+                _chain_outputs(out, "p%d_" % j, wl.mo.bufs[k % len(wl.mo.bufs)])
+    else:
+        if wl.dynamic:
+            out.update({"p0_flow_mix": wl.mix[0], "p0_frame_mix": wl.mix[1], "p0_fill_mask": wl.mix[2]})
+        else:
+            v = wl.r.views[0]
+            out.update({"p0_flow": wl.r.flows[0], "p0_rgb": v["rgb"], "p0_objmask": v["objmask"], "p0_rgb_u8": v["rgb_u8"]})
+        if wl.mo is not None:
+            _chain_outputs(out, "p0_", wl.mo.bufs[(wl.mo._next - 1) % len(wl.mo.bufs)])
+    return out
+
+
+def dump_outputs(tensors, path, budget=DUMP_BYTES, seed=0):
+    """Write every tensor as path/<name>.npy: float32, int64 as float64.  When all of them together exceed `budget` bytes, each array is
+    replaced by the same fraction of its elements at fixed indices (seeded, sorted; they depend only on the array's size)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for name, t in tensors.items():
+        a = t.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64 if a.dtype == np.int64 else np.float32)
+        arrays[name] = a
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in sorted(arrays.items()):
+        if total > budget:
+            a = a.ravel()[np.sort(np.random.default_rng(seed).choice(a.size, a.size * budget // total, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def cpu_baseline(S, H, W, pairs, budget_s=12.0, chain=True):
     """Time the oracle (checker, used here only as the reported CPU baseline) on the workload of `value`: full dynamic pairs + the
     moving-object chain of every pair (SURVEY 8(d)'s c3) - a bounded sample: pairs are rendered until `budget_s` seconds of CPU work have
@@ -721,11 +784,13 @@ def main():
         dt = float(t.item())
     else:
         total_pairs = my_pairs
+    if a.dump_outputs and rank == 0:
+        dump_outputs(last_step_outputs(wl, len(order)), a.dump_outputs)
 
     # the same pairs with the host work of a pair placed differently (outside the timed region; same box, seconds apart): what putting the per-pair pose
     # draws + homographies inside the timed region costs.  "once" = rounds 1-5's headline (fixed poses per image, prepared at set-up)
     host_prep_cmp = {}
-    if pipelined and not a.no_sub:
+    if a.full and pipelined and not a.no_sub:
         keep = wl.host_prep
         for mode in ("once", "per-pair", "window"):
             wl.host_prep = mode
@@ -746,10 +811,10 @@ def main():
                                    "host_prep_us_per_pair": (wl.host_seconds - h0) / nc * 1e6, "pairs": nc}
         wl.host_prep = keep
 
-    # BASELINE configs[3] beside the weak-scaling `value`, on every run: a FIXED batch of --batch images (512) sharded i % world over the ranks,
+    # --full: BASELINE configs[3] beside the weak-scaling `value`: a FIXED batch of --batch images (512) sharded i % world over the ranks,
     # each rank renders its share (cycling through its resident stacks); pairs/s = batch / slowest rank, per-rank seconds reported
     batch_rec = None
-    if a.mode == "resident" and a.batch > 0 and dynamic:
+    if a.full and a.mode == "resident" and a.batch > 0 and dynamic:
         mine_b = pipeline.shard_indices(a.batch, rank, world)
         order_b = list(range(len(mine_b)))
         wl.step(False, order_b[:8])
@@ -830,7 +895,7 @@ def main():
             wl.r.close()                                     # a CU-masked side stream (--chain-cu-stride)
         del wl
         torch.cuda.empty_cache()
-        if world == 1 and not a.no_sub and a.mode == "resident":
+        if a.full and world == 1 and not a.no_sub and a.mode == "resident":
             sub = []
             c3 = sub_record("c3 serial: BASELINE configs[2], 64x640x960 dynamic pair, one kernel after the other (per-kernel roofline entries)", 64, 640, 960, 4, dev, True, 5)
             sub.append(c3)
@@ -861,9 +926,9 @@ def main():
             out["sub"] = sub
             if dynamic:
                 out["overlap"] = overlap_record(S, H, W, dev)
-        if world == 1 and not a.no_sub:
+        if a.full and world == 1 and not a.no_sub:
             out["hbm_reference"] = hbm_reference(dev)
-        if world == 1 and not a.no_sub and not a.no_generator and a.mode == "resident":
+        if a.full and world == 1 and not a.no_sub and not a.no_generator and a.mode == "resident":
             try:
                 out["roofline_n1"] = n1_record(dev)
             except Exception as e:                                   # noqa: BLE001
@@ -895,7 +960,7 @@ def main():
                                                                   "~37 ms per image, so the generator is bound by it")
             except Exception as e:                                   # noqa: BLE001
                 out["generator_precise"] = {"error": repr(e)}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             torch.set_num_threads(host_threads)
             out["cpu_baseline"] = cpu_baseline(S, H, W, a.cpu_pairs, chain=chain)
             out["cpu_baseline"]["reference_measured_in_build_container"] = \

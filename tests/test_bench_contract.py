@@ -24,7 +24,7 @@ def _last_json(out):
 def test_single_gpu_line():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + SMALL, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     assert KEYS <= set(d) and "cpu_baseline" in d
@@ -105,7 +105,7 @@ def test_eight_ranks_self_launched_with_the_strong_scaling_record():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(MPIFLOW_DIST_BACKEND="gloo", MPIFLOW_FORCE_DEVICE="0")
     tiny = ["--planes", "8", "--height", "32", "--width", "64", "--images", "2", "--pairs-per-step", "0", "--steps", "2", "--warmup", "1", "--no-generator",
-            "--batch", "21"]
+            "--batch", "21", "--full"]
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8"] + tiny, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -152,7 +152,7 @@ def test_single_gpu_line_has_sub_records_and_names_the_dynamic_pair():
     8(d)'s full c3 (pair + moving-object chain); c2 / c1 / c5; the two-pipeline record; the end-to-end generator; the on-box HBM figures."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--images", "2", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--images", "2", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -209,3 +209,66 @@ def test_serial_pipeline_flag_keeps_the_round_2_structure():
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     assert d["config"]["pipeline"] == "serial" and "k_warp_composite_views" in d["roofline"]["kernel"] and "roofline_stage_ac" in d
+
+
+def test_plain_run_times_the_headline_only():
+    """Without --full the run sets up, warms up, times --steps steps and prints the line: `value` and `ms_per_step` of exactly those steps, the
+    headline roofline from their launches, and none of the records that take runs of their own."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    assert KEYS <= set(d) and d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "pairs/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - 2 * 3 / (d["ms_per_step"] * 3 / 1e3)) / d["value"] < 1e-6          # 2 pairs per step, 3 timed steps
+    assert abs(d["ms_per_step"] * 3 / 1e3 - d["config"]["timed_seconds"]) < 1e-9
+    rf = d["roofline"]
+    assert "k_pair_overlap" in rf["kernel"] and rf["launches_timed"] == 2 * 3 - 1
+    for k in ("cpu_baseline", "sub", "overlap", "batch512", "hbm_reference", "roofline_n1", "generator", "generator_precise", "generator_host_share_1of8"):
+        assert k not in d, k
+    c = d["config"]
+    assert c["host_prep_comparison"] is None and c["batch512_pairs_per_s"] is None and c["cpu_baseline_pairs_per_s"] is None
+    assert c["host_prep_us_per_pair_timed"] > 0
+
+
+def test_dump_outputs_are_the_same_run_after_run(tmp_path):
+    """--dump-outputs DIR: the last pairs of the last timed step (merged flow / frame / fill mask, the moving-object chain's results) as float
+    .npy files within 64 MB; the same arguments give the same inputs, so two runs write the same arrays."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs", str(d)] + SMALL, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1]))
+    for j in range(2):                                                      # 2 pairs per step: both are still resident
+        for k in ("flow_mix", "frame_mix", "fill_mask", "chain_flow_01", "chain_warped", "chain_mask_H"):
+            assert "p%d_%s.npy" % (j, k) in names, (j, k)
+    assert "p2_flow_mix.npy" not in names
+    assert sum(os.path.getsize(dirs[0] / n) for n in names) <= 64 * 10 ** 6
+    for n in names:
+        a, b = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape and (a.view(np.uint8) == b.view(np.uint8)).all(), n
+    flow, fill = np.load(dirs[0] / "p0_flow_mix.npy"), np.load(dirs[0] / "p0_fill_mask.npy")
+    assert flow.shape == (64, 96, 2) and fill.shape == (64, 96) and np.isfinite(flow).all() and np.abs(flow).max() > 0
+
+
+def test_dump_outputs_of_the_serial_forms(tmp_path):
+    """--dump-outputs on the one-kernel-after-the-other workload: the last pair's merged outputs and chain results (c3), the camera-only view (c2)."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import numpy as np
+    for form, extra, names in (("c3", ["--pipeline", "serial"], ("p0_flow_mix", "p0_frame_mix", "p0_fill_mask", "p0_chain_flow_01")),
+                               ("c2", ["--workload", "c2"], ("p0_flow", "p0_rgb", "p0_objmask", "p0_rgb_u8"))):
+        d = tmp_path / form
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs", str(d)] + extra + SMALL, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        got = sorted(n[:-4] for n in os.listdir(d))
+        for n in names:
+            assert n in got, (form, n)
+        assert not [n for n in got if n.startswith("p1_")]
+        for n in got:
+            a = np.load(d / (n + ".npy"))
+            assert a.dtype in (np.float32, np.float64) and a.shape[:2] in ((64, 96), (2, 64), (3, 64)) and np.isfinite(a).all(), (form, n, a.shape)

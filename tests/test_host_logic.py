@@ -1,5 +1,6 @@
 """CPU-only tests of the host logic: small-matrix maths vs goldens from the reference, parameter packing, the pose
 schedule replay, image sharding and the world_size-2 statistics all-reduce (gloo)."""
+import importlib.util
 import os
 import random
 import subprocess
@@ -300,6 +301,32 @@ def test_bench_gpus_flag_is_never_silently_ignored():
                        env=dict(clean, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0"))
     assert r.returncode != 0 and "they must agree" in r.stderr
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_bench_output_dump_is_bounded_and_seeded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: within the byte budget every array is written whole (uint8 -> float32, int64 -> float64); over it, every
+    array keeps the same share of its elements at seeded indices - the same files run after run - and the data stays within the budget."""
+    monkeypatch.delenv("HSA_ENABLE_IPC_MODE_LEGACY", raising=False)            # bench.py sets a default at import: restored after the test
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    t = {"flow": torch.rand((40, 60, 2), generator=g), "frame": torch.randint(0, 256, (40, 60, 3), dtype=torch.uint8, generator=g),
+         "index": torch.randint(0, 60, (40, 60), generator=g)}
+    bench.dump_outputs(t, str(tmp_path / "whole"))
+    for k, v in t.items():
+        a = np.load(tmp_path / "whole" / (k + ".npy"))
+        assert a.dtype == (np.float64 if k == "index" else np.float32) and a.shape == tuple(v.shape) and (a == v.numpy()).all()
+    budget = 8000
+    for d in ("one", "two"):
+        bench.dump_outputs(t, str(tmp_path / d), budget=budget)
+    data = 0
+    for k, v in t.items():
+        a, b = np.load(tmp_path / "one" / (k + ".npy")), np.load(tmp_path / "two" / (k + ".npy"))
+        assert a.ndim == 1 and 0 < a.size < v.numel() and bits_equal(a, b) == 0
+        assert np.isin(a, v.numpy().ravel().astype(a.dtype)).all()
+        data += a.nbytes
+    assert data <= budget
 
 
 def test_parameter_blocks_of_all_pairs_in_one_buffer_equal_the_per_block_packing():
