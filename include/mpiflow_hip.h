@@ -246,6 +246,31 @@ int mpf_stream_probe(const void *d_src, void *d_dst, size_t bytes, int mode, voi
  * (mod 256).  The host only deflates these bytes and wraps them in chunks (mpiflow_amd/io_formats.py). */
 int mpf_png_filter_up(const uint8_t *d_bgr, int H, int W, uint8_t *d_scanlines, void *stream);
 
+/* Training batches from rendered pairs (mpiflow_amd/online.py): RAFT's FlowAugmentor.spatial_transform (resize, flips, crop;
+ * RAFT/core/utils/augmentor.py:67-109) and its dataset's tensor packing (RAFT/core/datasets.py:85-90) in one pass.  One
+ * MpfAugmentSample per sample, in a HOST array of B (read by the launcher; the pointers in it are device pointers):
+ *   src, dst  u8 [H,W,3] BGR (image 1 = the source frame, image 2 = the filled target frame);  flow  f32 [H,W,2] (flow_mix)
+ *   resize    0: Hr == H, Wr == W, no resampling;  1: cv2 INTER_LINEAR to Hr x Wr (cv2: Wr = rint(W*scale_x), Hr = rint(H*scale_y)),
+ *             source coordinate (float)((d + 0.5) * (1.0 / scale) - 0.5), fp32 interpolation horizontal first, flow * (scale_x, scale_y)
+ *             in double then rounded to float
+ *   flip_h / flip_v  mirror the resized frame (and negate u / v);  y0, x0  crop origin in the resized, flipped frame
+ * -> d_image1, d_image2 f32 [B,3,h,w] RGB 0..255 (rintf, clamped);  d_flow f32 [B,2,h,w];  d_valid f32 [B,h,w] = |u| < 1000 && |v| < 1000.
+ * Identity (resize 0, no flips, crop = frame) reproduces the inputs exactly.  Validated before anything is launched (null pointers,
+ * B < 1, resize == 0 with Hr x Wr != H x W, a crop outside the resized frame).  One launch per 32 samples.  cv2's own u8 resize
+ * rounds 11-bit fixed-point weights and may differ by one LSB: unpinned (see mpf_augment.hip). */
+typedef struct MpfAugmentSample {
+    const uint8_t *src;
+    const uint8_t *dst;
+    const float *flow;
+    int resize;
+    double scale_x, scale_y;
+    int Hr, Wr;
+    int flip_h, flip_v;
+    int y0, x0;
+} MpfAugmentSample;
+int mpf_augment_pairs(const MpfAugmentSample *s, int B, int H, int W, int h, int w, float *image1, float *image2, float *flow, float *valid,
+                      void *stream);
+
 /* [3,H,W] float RGB -> [H,W,3] u8 BGR, clip(rint(x*255))  (utils/utils.py:174-177) */
 int mpf_to_u8_bgr(const float *d_img, int H, int W, uint8_t *d_out, void *stream);
 

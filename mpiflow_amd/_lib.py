@@ -74,6 +74,12 @@ class MpfMergeArgs(ctypes.Structure):
                 ("d_obj_mask", c_p), ("thresh", c_f), ("d_flow_mix", c_p), ("d_frame_mix", c_p), ("d_fill_mask", c_p), ("obj_mask_stride", c_i)]
 
 
+class MpfAugmentSample(ctypes.Structure):
+    """struct MpfAugmentSample of include/mpiflow_hip.h: one sample of mpf_augment_pairs (device pointers, crop / resize / flip parameters)."""
+    _fields_ = [("src", c_p), ("dst", c_p), ("flow", c_p), ("resize", c_i), ("scale_x", ctypes.c_double), ("scale_y", ctypes.c_double),
+                ("Hr", c_i), ("Wr", c_i), ("flip_h", c_i), ("flip_v", c_i), ("y0", c_i), ("x0", c_i)]
+
+
 MAX_VIEWS = 16          # MPF_MAX_VIEWS
 
 # name -> (restype, argtypes); must list every symbol include/mpiflow_hip.h declares (tests/test_capi.py checks)
@@ -104,6 +110,7 @@ SIGNATURES = {
     "mpf_pair_stats": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p]),
     "mpf_stream_probe": (c_i, [c_p, c_p, ctypes.c_size_t, c_i, c_p]),
     "mpf_to_u8_bgr": (c_i, [c_p, c_i, c_i, c_p, c_p]),
+    "mpf_augment_pairs": (c_i, [ctypes.POINTER(MpfAugmentSample), c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "mpf_src_xyz": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
     "mpf_transform_xyz": (c_i, [c_p, c_p, c_i, c_i64, c_p, c_p]),
     "mpf_homography_sample": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),

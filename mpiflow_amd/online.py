@@ -1,0 +1,555 @@
+"""Online pair source: rendered training pairs go straight into RAFT-layout batches on the GPU, nothing touches disk.
+
+    src = OnlinePairs(base, batch_size=8, crop=(288, 960), mpi_from="model", ckpt_path="random:3")
+    for batch in src:            # one epoch; dict(image1, image2 [B,3,h,w] RGB 0..255, flow [B,2,h,w], valid [B,h,w]) + batch["meta"]
+        loss = train_step(batch["image1"], batch["image2"], batch["flow"], batch["valid"])
+
+What a batch holds is what gen_3dphoto_dynamic.py would have written for the same seed and producer flags (same instance ids, poses,
+renders and hole fill), then RAFT's FlowAugmentor.spatial_transform (resize, stretch, flips, crop; RAFT/core/utils/augmentor.py:67-109)
+and its dataset's packing (RAFT/core/datasets.py:85-90), fused into one mpf_augment_pairs launch per batch.  Photometric augmentation
+(ColorJitter, eraser) stays with the trainer: it works on the returned tensors.
+
+Schedule contract (the CLI's, gen_3dphoto_dynamic.py main()): private random.Random(seed) / np.random.RandomState(seed) streams; per
+image with at least one instance in its mask, `pairs_per_image` x (instance id from numpy, dynamic pose, camera pose from `random`);
+images without one draw nothing and are skipped.  Every rank replays the whole schedule and renders the images i with i % world == rank.
+Epoch e+1 continues both streams where epoch e stopped.  shuffle=True: the image order of every epoch is a permutation drawn from a
+third private stream, and the schedule draws are consumed in that processing order.  A fourth private stream picks the samples of a
+batch out of the shuffle buffer (`mix` pairs; 0 = first in, first out) and draws their augmentation parameters.  The batches are a
+pure function of the arguments - not of `prefetch`, the fill pool or timing - and state_dict() / load_state_dict() resume them exactly.
+
+The source never touches the global `random`, `np.random` or torch RNGs, nor torch.set_num_threads.
+"""
+import collections
+import os
+import queue
+import random
+import threading
+
+import numpy as np
+import torch
+import torch.utils.data
+
+from . import _lib, host_math, io_formats, ops, pipeline, synth
+from .utils import utils as U
+
+MASK_THRESH = pipeline.MASK_THRESH
+
+
+def default_fill_threads():
+    """The CPUs this process may run on minus 4 (the producer thread, the decoders, the trainer's own thread), clamped to 2..32."""
+    try:
+        cores = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        cores = os.cpu_count() or 8
+    return max(2, min(32, cores - 4))
+
+
+def mpi_from_disparity(image_3HW, disp_HW, S):
+    """Stand-in MPI producer (the CLI's --mpi-from disparity): colours on every plane, sigma = 1e-4 except 50 on the plane nearest
+    to the pixel's disparity.  Returns (mpi [S,4,H,W], disparity [S])."""
+    planes = torch.from_numpy(synth.plane_disparities(S)).to(disp_HW.device)
+    idx = (disp_HW.unsqueeze(0) - planes.view(S, 1, 1)).abs().argmin(0)
+    sigma = torch.full((S,) + tuple(disp_HW.shape), 1e-4, dtype=torch.float32, device=disp_HW.device)
+    sigma.scatter_(0, idx.unsqueeze(0), 50.0)
+    mpi = torch.cat([image_3HW.unsqueeze(0).expand(S, -1, -1, -1), sigma.unsqueeze(1)], dim=1).contiguous()
+    return mpi, planes
+
+
+# ---- host side: the schedule and the augmentation draws (no GPU) ----------------------------------------------------------------
+
+class Schedule:
+    """The CLI's draw schedule on private streams.  draw(i, mask_max) -> (obj_indices, pose_params) or None (no instance: no draws)."""
+
+    def __init__(self, seed, ext_cz, pairs_per_image, poses="v2"):
+        self.rng = random.Random(seed)
+        self.nrs = np.random.RandomState(seed)
+        self.ext_cz, self.R, self.poses = ext_cz, pairs_per_image, poses
+
+    def draw(self, mask_max):
+        if mask_max <= 0:
+            return None
+        obj_indices, pose_params = [], []
+        for _ in range(self.R):
+            obj_indices.append(int(self.nrs.randint(mask_max)) + 1)                                                         # :101
+            pose_params.append(host_math.draw_pose_parameters(self.ext_cz, rng=self.rng, profile=self.poses))                 # utils.py:207
+            pose_params.append(host_math.draw_pose_parameters(self.ext_cz, base_motions=[0, 0, 0], rng=self.rng, profile=self.poses))   # :208
+        return obj_indices, pose_params
+
+    def state(self):
+        return dict(rng=self.rng.getstate(), nrs=self.nrs.get_state())
+
+    def set_state(self, st):
+        self.rng.setstate(st["rng"])
+        self.nrs.set_state(st["nrs"])
+
+
+def augment_params(rs, H, W, crop, augment):
+    """One sample's parameters by RAFT's FlowAugmentor.spatial_transform rules (augmentor.py:67-109), drawn from the RandomState `rs`:
+    min_scale clip max((h+8)/H, (w+8)/W); scale = 2**U(min_scale, max_scale); stretch with probability 0.8 (2**U(-0.2, 0.2) per axis);
+    resize with probability 0.8 (cv2's size: rint(W * scale_x), rint(H * scale_y)); h-flip 0.5 and v-flip 0.1 when do_flip;
+    y0 = randint(0, Hr - h), x0 = randint(0, Wr - w) (0 without a draw when equal).  augment=None: no resize, no flips, crop only."""
+    h, w = crop
+    p = dict(resize=0, scale_x=1.0, scale_y=1.0, Hr=H, Wr=W, flip_h=0, flip_v=0, y0=0, x0=0)
+    if augment is not None:
+        a = dict(min_scale=-0.2, max_scale=0.5, do_flip=True, stretch_prob=0.8, max_stretch=0.2, spatial_aug_prob=0.8, h_flip_prob=0.5, v_flip_prob=0.1)
+        a.update(augment)
+        min_scale = np.maximum((h + 8) / float(H), (w + 8) / float(W))
+        scale = 2 ** rs.uniform(a["min_scale"], a["max_scale"])
+        scale_x = scale_y = scale
+        if rs.rand() < a["stretch_prob"]:
+            scale_x *= 2 ** rs.uniform(-a["max_stretch"], a["max_stretch"])
+            scale_y *= 2 ** rs.uniform(-a["max_stretch"], a["max_stretch"])
+        scale_x = float(np.clip(scale_x, min_scale, None))
+        scale_y = float(np.clip(scale_y, min_scale, None))
+        if rs.rand() < a["spatial_aug_prob"]:
+            p.update(resize=1, scale_x=scale_x, scale_y=scale_y, Hr=int(np.rint(H * scale_y)), Wr=int(np.rint(W * scale_x)))
+        if a["do_flip"]:
+            if rs.rand() < a["h_flip_prob"]:
+                p["flip_h"] = 1
+            if rs.rand() < a["v_flip_prob"]:
+                p["flip_v"] = 1
+    if p["Hr"] < h or p["Wr"] < w:
+        raise ValueError("crop %s does not fit the %d x %d frame" % (crop, p["Hr"], p["Wr"]))
+    p["y0"] = int(rs.randint(0, p["Hr"] - h)) if p["Hr"] > h else 0
+    p["x0"] = int(rs.randint(0, p["Wr"] - w)) if p["Wr"] > w else 0
+    return p
+
+
+class _Stop(Exception):
+    pass
+
+
+class OnlinePairs:
+    """Iterable source of augmented training batches rendered on the GPU (module docstring).  Iterating yields one epoch.
+
+    base: the CLI's input layout (base/{images,disps,masks}[, mpis]).  crop: (h, w), None = the full frame.  mpi_from: model | npz | disparity;
+    ckpt_path: checkpoint or "random:SEED" (model); model_dtype: auto | fp16 (HipPredictor, graph) or fp32 | fp32-mfma | fp64 (PrecisePredictor).
+    fill: auto | builtin | peel | none (the CLI's --inpaint; cv2 where installed).  augment: dict of RAFT's FlowAugmentor settings, None = none.
+    mix: shuffle-buffer size in pairs (0 = off).  prefetch: batches enqueued ahead of the consumer.  rank / world_size: default from
+    torch.distributed or RANK / WORLD_SIZE.  fill_threads: host threads of fill="builtin" (default: default_fill_threads())."""
+
+    def __init__(self, base, batch_size=8, crop=(288, 960), width=1280, height=384, seed=114514, ext_cz=0.15, pairs_per_image=5, poses="v2",
+                 mpi_from="model", ckpt_path=None, model_dtype="auto", fill="auto", augment=dict(min_scale=-0.2, max_scale=0.5, do_flip=True),
+                 shuffle=True, mix=32, prefetch=2, rank=None, world_size=None, device=None, planes=64, fill_threads=None):
+        if torch.utils.data.get_worker_info() is not None:
+            raise RuntimeError("OnlinePairs renders on the GPU in the training process: construct it there, not inside a DataLoader worker")
+        if mpi_from not in ("model", "npz", "disparity"):
+            raise ValueError("mpi_from must be model, npz or disparity")
+        if batch_size < 1 or pairs_per_image < 1 or mix < 0 or prefetch < 0:
+            raise ValueError("batch_size and pairs_per_image must be >= 1, mix and prefetch >= 0")
+        self.base, self.B, self.W, self.H = base, int(batch_size), int(width), int(height)
+        self.crop = (self.H, self.W) if crop is None else (int(crop[0]), int(crop[1]))
+        if self.crop[0] > self.H or self.crop[1] > self.W:
+            raise ValueError("crop %s is larger than the %d x %d frame" % (self.crop, self.H, self.W))
+        self.seed, self.ext_cz, self.R, self.poses = int(seed), float(ext_cz), int(pairs_per_image), poses
+        self.mpi_from, self.augment, self.shuffle, self.mix, self.prefetch = mpi_from, (None if augment is None else dict(augment)), shuffle, int(mix), int(prefetch)
+        if rank is None or world_size is None:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized():
+                r, w = dist.get_rank(), dist.get_world_size()
+            else:
+                r, w = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
+            rank = r if rank is None else rank
+            world_size = w if world_size is None else world_size
+        if not 0 <= rank < world_size:
+            raise ValueError("rank %d outside world %d" % (rank, world_size))
+        self.rank, self.world = int(rank), int(world_size)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.MpiFlowHipError("OnlinePairs renders with the HIP kernels of mpiflow_amd: device must be a GPU")
+        _lib.load()
+        fm = U.resolve_inpaint(fill)
+        if fm not in ("cv2", "builtin", "peel", "none"):
+            raise ValueError("fill must be auto, builtin, peel or none")
+        self.fill = fm
+        self.fill_threads = int(fill_threads) if fill_threads else default_fill_threads()
+
+        self.img_dir, self.disp_dir, self.mask_dir = (os.path.join(base, d) for d in ("images", "disps", "masks"))
+        self.names = sorted(os.listdir(self.img_dir))
+        self.mask_max = self._mask_table()
+        self.skipped = []
+        self._skipped_names = set()
+
+        # the four private streams and the position: everything state_dict() captures
+        self._sched = Schedule(self.seed, self.ext_cz, self.R, poses)
+        self._order_rs = np.random.RandomState([self.seed & 0xFFFFFFFF, 2])
+        self._aug_rs = np.random.RandomState([self.seed & 0xFFFFFFFF, 1])
+        self._epoch, self._pos, self._order, self._batches = 0, 0, None, 0
+        self._buf = []                    # shuffle buffer: dicts(job, r, src, dst, flow, wait)
+        self._pending = []                # the pairs of the image rendered last: they join the buffer when the next image has been enqueued
+        self._resume_buf = []             # (job, r) to re-render before anything else (load_state_dict): the buffer, then the pending pairs
+        self._resume_pending = 0
+
+        self._model = self._predictor = None
+        self._set_up_gpu(ckpt_path, model_dtype, planes)
+        self._producer = None
+        self._q = None
+        self._stop = threading.Event()
+        self._delivered = self._snapshot()
+        self._closed = False
+
+    # ---- set-up ------------------------------------------------------------------------------------------------------------------
+    def _mask_table(self):
+        import concurrent.futures
+        import torch.distributed as dist
+        if self.world > 1 and dist.is_available() and dist.is_initialized() and dist.get_world_size() == self.world:
+            return pipeline.mask_max_table(self.names, self.mask_dir, self.rank, self.world)
+        with concurrent.futures.ThreadPoolExecutor(max_workers=8) as pool:
+            return list(pool.map(lambda nm: io_formats.mask_max_of_file(os.path.join(self.mask_dir, nm)), self.names))
+
+    def _set_up_gpu(self, ckpt_path, model_dtype, planes):
+        dev = self.device
+        self.planes = int(planes)
+        with torch.cuda.device(dev):
+            self.stream = torch.cuda.Stream(device=dev)              # rendering, fill on the device, augmentation
+            self.upload_stream = torch.cuda.Stream(device=dev)       # filled frames of fill="builtin" back to the device
+            self.tail = torch.cuda.Stream(device=dev)                # hole fill (peel) / copies of the frames to the host (builtin)
+            self.stream.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(self.stream):
+                if self.mpi_from == "model":
+                    from .model import MPIPredictor
+                    if ckpt_path is None:
+                        raise ValueError("mpi_from='model' needs ckpt_path (a checkpoint, or random:SEED)")
+                    with torch.random.fork_rng(devices=[]):           # module construction draws default initialisations from torch's global RNG
+                        if str(ckpt_path).startswith("random:"):
+                            model = MPIPredictor(self.W, self.H, self.planes).randomize_(int(str(ckpt_path).split(":")[1])).eval().to(dev)
+                        else:
+                            if not os.path.exists(ckpt_path):
+                                raise FileNotFoundError("checkpoint %r not found" % (ckpt_path,))
+                            model = MPIPredictor.from_checkpoint(ckpt_path, self.W, self.H).to(dev)
+                            self.planes = model.num_planes
+                    precise = {"fp32": torch.float32, "fp32-mfma": torch.float32, "fp64": torch.float64}.get(model_dtype)
+                    if precise is not None:
+                        from .model.precise import PrecisePredictor
+                        self._predictor = PrecisePredictor(model, dtype=precise, x3=model_dtype == "fp32")
+                    elif model_dtype in ("auto", "fp16"):
+                        from .model.engine import HipPredictor
+                        self._predictor = HipPredictor(model, graph=True)
+                        # capture the network's graph here, on the constructing thread, not in the producer while other threads use the device
+                        self._predictor(torch.zeros((1, 3, self.H, self.W), device=dev), torch.full((1, 1, self.H, self.W), 0.5, device=dev))
+                    else:
+                        raise ValueError("model_dtype must be auto, fp16, fp32, fp32-mfma or fp64")
+                    self._model = model
+                self.renderer = pipeline.PairRenderer(self.planes, self.H, self.W, dev)
+                self.inputs = dict(image=torch.empty((3, self.H, self.W), device=dev), disp=torch.empty((self.H, self.W), device=dev))
+                self.fill_ws = torch.empty(int(_lib.load().mpf_fill_holes_workspace(self.H, self.W)), dtype=torch.uint8, device=dev)
+            K = torch.tensor([[0.58, 0, 0.5], [0, 0.58, 0.5], [0, 0, 1]])      # gen_3dphoto_dynamic_v2.py:42-49
+            K[0, :] *= self.W
+            K[1, :] *= self.H
+            self.K = K.unsqueeze(0)
+        self._pool = None
+        self._slots = []
+        if self.fill in ("cv2", "builtin"):
+            import concurrent.futures
+            self._pool = concurrent.futures.ThreadPoolExecutor(max_workers=self.fill_threads, thread_name_prefix="online-fill")
+            self._free_slots = collections.deque()
+            self._busy_slots = collections.deque()               # (slot, upload event) in submission order
+            self._n_slots = 2 * self.fill_threads + 2
+        self.stream.synchronize()
+
+    # ---- state -------------------------------------------------------------------------------------------------------------------
+    def _snapshot(self):
+        return dict(epoch=self._epoch, pos=self._pos, order=None if self._order is None else list(self._order), batches=self._batches,
+                    sched=self._sched.state(), order_rs=self._order_rs.get_state(), aug_rs=self._aug_rs.get_state(),
+                    buffer=[(e["job"], e["r"]) for e in self._buf + self._pending] if not self._resume_buf else list(self._resume_buf),
+                    pending=len(self._pending) if not self._resume_buf else self._resume_pending)
+
+    def state_dict(self):
+        """The position after the last batch (or epoch end) handed to the consumer: epoch, image position, all four streams and the
+        identities of the pairs waiting in the shuffle buffer (re-rendered on resume)."""
+        import copy
+        return copy.deepcopy(self._delivered)
+
+    def load_state_dict(self, st):
+        import copy
+        self._stop_producer()
+        st = copy.deepcopy(st)
+        self._epoch, self._pos, self._order, self._batches = st["epoch"], st["pos"], st["order"], st["batches"]
+        self._sched.set_state(st["sched"])
+        self._order_rs.set_state(st["order_rs"])
+        self._aug_rs.set_state(st["aug_rs"])
+        self._buf, self._pending = [], []
+        self._resume_buf = [(dict(job), r) for job, r in st["buffer"]]
+        self._resume_pending = st["pending"]
+        self._delivered = self._snapshot()
+
+    # ---- iteration ---------------------------------------------------------------------------------------------------------------
+    def __iter__(self):
+        if self._closed:
+            raise RuntimeError("OnlinePairs is closed")
+        if self._producer is None:
+            self._q = queue.Queue(maxsize=max(1, self.prefetch))
+            self._stop.clear()
+            self._producer = threading.Thread(target=self._produce, name="online-pairs", daemon=True)
+            self._producer.start()
+        while True:
+            kind, payload, snap = self._q.get()
+            if kind == "error":
+                self._producer.join()
+                self._producer = None
+                raise payload
+            self._delivered = snap
+            if kind == "end":
+                return
+            yield self._hand_over(payload)
+
+    def _hand_over(self, item):
+        batch, ready = item
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(ready)
+        for k in ("image1", "image2", "flow", "valid"):
+            batch[k].record_stream(cur)
+        return batch
+
+    def _put(self, kind, payload):
+        snap = self._snapshot()
+        while True:
+            if self._stop.is_set():
+                raise _Stop()
+            try:
+                self._q.put((kind, payload, snap), timeout=0.1)
+                return
+            except queue.Full:
+                continue
+
+    def _produce(self):
+        try:
+            with torch.cuda.device(self.device), torch.no_grad():
+                self._run()
+        except _Stop:
+            pass
+        except BaseException as e:                                         # noqa: BLE001 - handed to the consumer
+            try:
+                self._q.put(("error", e, None), timeout=5)
+            except queue.Full:
+                pass
+
+    def _run(self):
+        cap = max(self.mix, self.B)
+        if self._resume_buf:
+            jobs = collections.OrderedDict()
+            for job, r in self._resume_buf:
+                jobs.setdefault(job["i"], (job, []))[1].append(r)
+            rendered = {}
+            items = iter(io_formats.InputPrefetcher(self.names, self.img_dir, self.disp_dir, self.mask_dir, list(jobs)))
+            for i, (job, rs) in jobs.items():
+                item = next(items)
+                rendered[i] = {e["r"]: e for e in self._render(job, item, rs)}
+            entries = [rendered[job["i"]][r] for job, r in self._resume_buf]
+            cut = len(entries) - self._resume_pending
+            self._buf, self._pending = entries[:cut], entries[cut:]
+            self._resume_buf, self._resume_pending = [], 0
+        while True:
+            n = len(self.names)
+            if self._order is None:
+                self._order = [int(v) for v in self._order_rs.permutation(n)] if self.shuffle else list(range(n))
+            owned = [i for i in self._order[self._pos:] if i % self.world == self.rank and self.mask_max[i] > 0]
+            items = iter(io_formats.InputPrefetcher(self.names, self.img_dir, self.disp_dir, self.mask_dir, owned))
+            while self._pos < n:
+                i = self._order[self._pos]
+                self._pos += 1
+                name = self.names[i].split(".")[0]
+                drawn = self._sched.draw(self.mask_max[i])
+                if drawn is None:
+                    if i % self.world == self.rank:
+                        self._skip(name, "mask unreadable" if self.mask_max[i] < 0 else "mask holds no instance")
+                    continue
+                if i % self.world != self.rank:
+                    continue
+                item = next(items)
+                assert item["i"] == i
+                if item["error"] is not None:
+                    self._skip(name, "input: %r" % (item["error"],))
+                    continue
+                job = dict(i=i, name=name, obj_indices=drawn[0], pose_params=drawn[1])
+                try:
+                    fresh = self._render(job, item, range(self.R))
+                except _Stop:
+                    raise
+                except Exception as e:                                     # noqa: BLE001 - isolate the image, as the CLI does
+                    self.stream.synchronize()
+                    self._skip(name, "render: %r" % (e,))
+                    continue
+                # batches draw from the pairs of the images BEFORE this one: their host fills ran while this image was enqueued, so forming a
+                # batch rarely waits for one, and the GPU already has this image's work (deterministic: the lag is one image, not a time)
+                self._buf += self._pending
+                self._pending = fresh
+                while len(self._buf) >= cap:
+                    self._put("batch", self._batch())
+            self._buf += self._pending
+            self._pending = []
+            while len(self._buf) >= self.B:
+                self._put("batch", self._batch())
+            self._epoch, self._pos, self._order = self._epoch + 1, 0, None
+            self._put("end", None)
+
+    def _skip(self, name, why):
+        if name not in self._skipped_names:
+            self._skipped_names.add(name)
+            self.skipped.append((name, why))
+
+    # ---- rendering -----------------------------------------------------------------------------------------------------------------
+    def _render(self, job, item, keep):
+        """One image: upload, input stage, MPI producer + blend, its pairs, hole fill.  -> buffer entries for the pairs r in `keep`."""
+        dev, H, W, ren = self.device, self.H, self.W, self.renderer
+        keep = list(keep)
+        with torch.cuda.stream(self.stream):
+            rgb8 = item["rgb_u8"].to(dev, non_blocking=True)
+            dsp8 = item["disp_u8"].to(dev, non_blocking=True)
+            ids = item["ids_u8"].to(dev, non_blocking=True)
+            if rgb8.shape[:2] == dsp8.shape[:2]:
+                pre = ops.prepare_inputs(rgb_u8=rgb8, disp_u8=dsp8, size=(H, W), out=self.inputs)
+            else:
+                pre = dict(image=ops.prepare_inputs(rgb_u8=rgb8, size=(H, W), out=self.inputs)["image"],
+                           disp=ops.prepare_inputs(disp_u8=dsp8, size=(H, W), out=self.inputs)["disp"])
+            image, disp = pre["image"][None], pre["disp"][None, None]
+            cum_mask = None
+            if self.mpi_from == "npz":
+                z = np.load(os.path.join(self.base, "mpis", job["name"] + ".npz"))
+                mpi, planes = torch.from_numpy(z["mpi"]).to(dev), torch.from_numpy(z["disparity"]).to(dev)
+            elif self._predictor is not None:
+                mpi, cum_mask, planes = self._predictor(image, disp)
+            else:
+                mpi, planes = mpi_from_disparity(image[0], disp[0, 0], self.planes)
+            ren.blend(mpi, image[0], self.K, planes, cum_mask=cum_mask)
+            src = ren.src_u8.clone()                                     # the renderer's buffer is the next image's
+            poses = host_math.poses_from_parameters(job["pose_params"])
+            obj_masks = [ops.prepare_inputs(ids_u8=ids, obj_index=k, size=(H, W))["mask"] for k in job["obj_indices"]]
+            results = ren.run_pairs(mpi, image[0], self.K, planes, obj_masks, [(poses[2 * r + 1], poses[2 * r]) for r in range(self.R)],
+                                    cum_mask=cum_mask)
+            rendered = torch.cuda.Event()
+            rendered.record(self.stream)
+            dsts = [torch.empty((H, W, 3), dtype=torch.uint8, device=dev) for _ in keep] if self.fill == "peel" else None
+        # the fills run on a second stream, as the CLI's tail stream: the one-workgroup peel kernels / the copies to the host overlap the next
+        # image's network instead of running in front of it.  Everything they read or write was allocated on self.stream and stays referenced
+        # by the buffer entry until the batch that consumes it has been enqueued behind them (mpf_augment_pairs waits for `filled`).
+        self.tail.wait_event(rendered)
+        out = []
+        with torch.cuda.stream(self.tail):
+            for n, r in enumerate(keep):
+                res = results[r]
+                e = dict(job=job, r=r, src=src, flow=res["flow_mix"], wait=None, keep=res["slab"])
+                if self.fill == "peel":
+                    e["dst"] = ops.fill_holes(res["frame_mix"], res["fill_mask"], out=dsts[n], workspace=self.fill_ws)
+                elif self.fill == "none":
+                    e["dst"] = res["frame_mix"]
+                else:
+                    e["dst"], e["wait"] = self._host_fill(res["frame_mix"], res["fill_mask"])
+                out.append(e)
+            if self.fill in ("peel", "none"):
+                filled = torch.cuda.Event()
+                filled.record(self.tail)
+                for e in out:
+                    e["wait"] = filled
+        return out
+
+    def _slot(self):
+        if self._free_slots:
+            return self._free_slots.popleft()
+        if len(self._free_slots) + len(self._busy_slots) < self._n_slots:
+            pin = lambda *shape: torch.empty(shape, dtype=torch.uint8).pin_memory()    # noqa: E731
+            return dict(frame=pin(self.H, self.W, 3), hole=pin(self.H, self.W), out=pin(self.H, self.W, 3))
+        slot, fut = self._busy_slots.popleft()                            # the oldest: reused only after its upload has completed
+        fut.result().synchronize()
+        return slot
+
+    def _host_fill(self, frame_mix, fill_mask):
+        """fill="builtin" | "cv2": frame + hole mask to a pinned slot (on the render stream), fill on a pool thread, upload on the upload
+        stream.  -> (device frame, future of the upload's event)."""
+        while self._busy_slots and self._busy_slots[0][1].done() and self._busy_slots[0][1].result().query():
+            self._free_slots.append(self._busy_slots.popleft()[0])
+        slot = self._slot()
+        slot["frame"].copy_(frame_mix, non_blocking=True)
+        slot["hole"].copy_(fill_mask, non_blocking=True)
+        copied = torch.cuda.Event()
+        copied.record(torch.cuda.current_stream())
+        with torch.cuda.stream(self.stream):                             # allocated where it is consumed
+            dst = torch.empty((self.H, self.W, 3), dtype=torch.uint8, device=self.device)
+        fill, dev, up = self.fill, self.device, self.upload_stream
+
+        def work():
+            copied.synchronize()
+            if fill == "cv2":
+                import cv2
+                slot["out"].numpy()[...] = cv2.inpaint(slot["frame"].numpy(), slot["hole"].numpy(), 3, cv2.INPAINT_NS)
+            else:
+                ops.inpaint_host(slot["frame"].numpy(), slot["hole"].numpy(), 3, ops.INPAINT_NS, out=slot["out"].numpy())
+            with torch.cuda.device(dev), torch.cuda.stream(up):
+                dst.copy_(slot["out"], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(up)
+            return ev
+        fut = self._pool.submit(work)
+        self._busy_slots.append((slot, fut))
+        return dst, fut
+
+    # ---- batches -------------------------------------------------------------------------------------------------------------------
+    def _batch(self):
+        """B entries out of the buffer (uniformly from the augmentation stream when mixing, first in first out otherwise), their augmentation
+        parameters, one mpf_augment_pairs launch.  -> (batch dict, ready event)."""
+        if self.mix > 0:
+            picks = [int(v) for v in self._aug_rs.choice(len(self._buf), self.B, replace=False)]
+            taken = [self._buf[j] for j in picks]
+            gone = set(picks)
+            self._buf = [e for j, e in enumerate(self._buf) if j not in gone]
+        else:
+            taken, self._buf = self._buf[:self.B], self._buf[self.B:]
+        params = [augment_params(self._aug_rs, self.H, self.W, self.crop, self.augment) for _ in taken]
+        with torch.cuda.stream(self.stream):
+            for e in taken:
+                if e["wait"] is not None:
+                    self.stream.wait_event(e["wait"] if isinstance(e["wait"], torch.cuda.Event) else e["wait"].result())
+            samples = [dict(src=e["src"], dst=e["dst"], flow=e["flow"], **p) for e, p in zip(taken, params)]
+            out = ops.augment_pairs(samples, size=self.crop)
+            ready = torch.cuda.Event()
+            ready.record(self.stream)
+        self._batches += 1
+        out["meta"] = [(e["job"]["name"], e["r"], e["job"]["obj_indices"][e["r"]], p["scale_x"], p["scale_y"], p["flip_h"], p["flip_v"], p["y0"], p["x0"])
+                       for e, p in zip(taken, params)]
+        return out, ready
+
+    # ---- teardown ------------------------------------------------------------------------------------------------------------------
+    def _stop_producer(self):
+        if self._producer is None:
+            return
+        self._stop.set()
+        while self._producer.is_alive():
+            try:
+                self._q.get(timeout=0.05)
+            except queue.Empty:
+                pass
+        self._producer.join()
+        self._producer = None
+        self._stop.clear()
+        # the producer ran ahead of the consumer: rewind to what was delivered
+        delivered = self._delivered
+        self.stream.synchronize()
+        self.load_state_dict(delivered)
+
+    def close(self):
+        if self._closed:
+            return
+        self._stop_producer()
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
+            self._pool = None
+        self.stream.synchronize()
+        self.upload_stream.synchronize()
+        self.tail.synchronize()
+        self._buf, self._pending, self._resume_buf = [], [], []
+        self._free_slots = self._busy_slots = collections.deque()
+        self.renderer = self._predictor = self._model = None
+        self._closed = True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                                                  # noqa: BLE001
+            pass

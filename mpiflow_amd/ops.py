@@ -449,6 +449,48 @@ def png_scanlines(img_HW3_bgr_u8, out=None):
     return out
 
 
+def augment_pairs(samples, out=None, size=None):
+    """RAFT's spatial augmentation + tensor packing of a batch of pairs in one launch (mpf_augment_pairs), on the current stream.
+    samples: B dicts with src / dst (u8 [H,W,3] BGR) and flow (f32 [H,W,2]) on the device, and resize, scale_x, scale_y, Hr, Wr, flip_h, flip_v,
+    y0, x0 (missing keys: identity - no resize, no flips, origin 0).  The crop size is out's, else `size` = (h, w), else the frame's.
+    -> dict(image1, image2 [B,3,h,w] RGB 0..255, flow [B,2,h,w], valid [B,h,w]), all fp32; `out` may carry these four tensors."""
+    lib = _lib.load()
+    B = len(samples)
+    if B < 1:
+        raise ValueError("augment_pairs: no samples")
+    src0 = _dev(samples[0]["src"], "src", torch.uint8)
+    H, W, _ = src0.shape
+    dev = src0.device
+    if out is not None:
+        h, w = out["valid"].shape[-2:]
+    else:
+        h, w = size if size is not None else (H, W)
+        out = dict(image1=torch.empty((B, 3, h, w), dtype=_f32, device=dev), image2=torch.empty((B, 3, h, w), dtype=_f32, device=dev),
+                   flow=torch.empty((B, 2, h, w), dtype=_f32, device=dev), valid=torch.empty((B, h, w), dtype=_f32, device=dev))
+    for k, shape in (("image1", (B, 3, h, w)), ("image2", (B, 3, h, w)), ("flow", (B, 2, h, w)), ("valid", (B, h, w))):
+        t = out[k]
+        if tuple(t.shape) != shape or t.dtype != _f32 or not t.is_contiguous() or t.device != dev:
+            raise ValueError("augment_pairs: out[%r] must be a contiguous fp32 %s tensor on %s" % (k, shape, dev))
+    arr = (_lib.MpfAugmentSample * B)()
+    keep = []
+    with torch.cuda.device(dev):
+        for b, s in enumerate(samples):
+            src, dst, flow = _dev(s["src"], "src", torch.uint8), _dev(s["dst"], "dst", torch.uint8), _dev(s["flow"], "flow")
+            if tuple(src.shape) != (H, W, 3) or tuple(dst.shape) != (H, W, 3) or tuple(flow.shape) != (H, W, 2):
+                raise ValueError("augment_pairs: sample %d: src / dst must be [%d,%d,3], flow [%d,%d,2]" % (b, H, W, H, W))
+            keep += [src, dst, flow]
+            a = arr[b]
+            a.src, a.dst, a.flow = src.data_ptr(), dst.data_ptr(), flow.data_ptr()
+            a.resize = int(s.get("resize", 0))
+            a.scale_x, a.scale_y = float(s.get("scale_x", 1.0)), float(s.get("scale_y", 1.0))
+            a.Hr, a.Wr = int(s.get("Hr", H)), int(s.get("Wr", W))
+            a.flip_h, a.flip_v = int(bool(s.get("flip_h", 0))), int(bool(s.get("flip_v", 0)))
+            a.y0, a.x0 = int(s.get("y0", 0)), int(s.get("x0", 0))
+        _lib.check(lib.mpf_augment_pairs(arr, B, H, W, h, w, _ptr(out["image1"]), _ptr(out["image2"]), _ptr(out["flow"]), _ptr(out["valid"]), _stream()),
+                   "mpf_augment_pairs")
+    return out
+
+
 @_on_device
 def to_u8_bgr(img_3HW):
     lib = _lib.load()
