@@ -271,6 +271,42 @@ typedef struct MpfAugmentSample {
 int mpf_augment_pairs(const MpfAugmentSample *s, int B, int H, int W, int h, int w, float *image1, float *image2, float *flow, float *valid,
                       void *stream);
 
+/* The photometric half of RAFT's FlowAugmentor (color_transform + eraser_transform, RAFT/core/utils/augmentor.py:36-65), which it runs on the
+ * full-size u8 frames before spatial_transform: run it before mpf_augment_pairs, whose src / dst it writes.  One MpfPhotoSample per sample,
+ * in a HOST array of B (the pointers in it are device pointers):
+ *   src, dst  u8 [H,W,3] BGR (image 1, image 2), read with RGB semantics (R = byte 2);  src_out, dst_out  u8 [H,W,3] BGR results (may be
+ *             src / dst themselves; no other overlap)
+ *   jitter    torchvision ColorJitter on a PIL RGB image: the ops order[0 .. n_ops) in that order, 0 brightness blend(0, x, f),
+ *             1 contrast blend(m, x, f) with m = int(sumL / n + 0.5) over the image as it stands before the op, 2 saturation
+ *             blend(L(x), x, f), 3 hue: PIL's RGB -> HSV, H = (H + hue_shift) & 255, PIL's HSV -> RGB (lossy even at shift 0).
+ *             L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16;  blend(a, x, f) = (float)a + f * (float)(x - a) in fp32, clamped, truncated.
+ *   joint     1: jitter[0] on both frames, one contrast mean over both (RAFT's symmetric jitter of the stacked pair);  0: jitter[0] on src,
+ *             jitter[1] on dst, each its own mean
+ *   n_rect, rect  0..2 rectangles {x0, y0, dx, dy} filled, after the jitter, on dst_out with its mean colour sum_c // (H W) (RAFT's eraser);
+ *             clipped at the frame edge
+ * d_workspace: mpf_photometric_workspace(B) bytes, 8-byte aligned; zeroed on the stream by the call.  Validated before anything is launched
+ * (null pointers, B < 1, a bad shape, op orders that are not distinct values in 0..3, non-finite or negative factors, a hue shift outside
+ * -128..127, n_rect outside 0..2, a rectangle origin outside the frame or an extent < 1, a short or misaligned workspace).  At most three
+ * launches per 32 samples; integer sums with integer atomics: repeated runs are byte-identical.  Contract in full: mpf_photometric.hip. */
+typedef struct MpfPhotoJitter {
+    int n_ops;                   /* 0..4 */
+    int order[4];                /* op codes of the chain, order[0] first */
+    float brightness, contrast, saturation;   /* factors, finite, >= 0 (read when their op is in the chain) */
+    int hue_shift;               /* int(hue * 255.0) truncated toward zero, -128..127 */
+} MpfPhotoJitter;
+typedef struct MpfPhotoSample {
+    const uint8_t *src;
+    const uint8_t *dst;
+    uint8_t *src_out;
+    uint8_t *dst_out;
+    int joint;
+    MpfPhotoJitter jitter[2];
+    int n_rect;
+    int rect[2][4];              /* x0, y0, dx, dy */
+} MpfPhotoSample;
+size_t mpf_photometric_workspace(int B);
+int mpf_photometric_pairs(const MpfPhotoSample *s, int B, int H, int W, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* [3,H,W] float RGB -> [H,W,3] u8 BGR, clip(rint(x*255))  (utils/utils.py:174-177) */
 int mpf_to_u8_bgr(const float *d_img, int H, int W, uint8_t *d_out, void *stream);
 

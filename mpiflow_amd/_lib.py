@@ -80,6 +80,17 @@ class MpfAugmentSample(ctypes.Structure):
                 ("Hr", c_i), ("Wr", c_i), ("flip_h", c_i), ("flip_v", c_i), ("y0", c_i), ("x0", c_i)]
 
 
+class MpfPhotoJitter(ctypes.Structure):
+    """struct MpfPhotoJitter of include/mpiflow_hip.h: one ColorJitter parameter set of mpf_photometric_pairs."""
+    _fields_ = [("n_ops", c_i), ("order", c_i * 4), ("brightness", c_f), ("contrast", c_f), ("saturation", c_f), ("hue_shift", c_i)]
+
+
+class MpfPhotoSample(ctypes.Structure):
+    """struct MpfPhotoSample of include/mpiflow_hip.h: one sample of mpf_photometric_pairs (device pointers, jitter, eraser rectangles)."""
+    _fields_ = [("src", c_p), ("dst", c_p), ("src_out", c_p), ("dst_out", c_p), ("joint", c_i), ("jitter", MpfPhotoJitter * 2), ("n_rect", c_i),
+                ("rect", (c_i * 4) * 2)]
+
+
 MAX_VIEWS = 16          # MPF_MAX_VIEWS
 
 # name -> (restype, argtypes); must list every symbol include/mpiflow_hip.h declares (tests/test_capi.py checks)
@@ -111,6 +122,8 @@ SIGNATURES = {
     "mpf_stream_probe": (c_i, [c_p, c_p, ctypes.c_size_t, c_i, c_p]),
     "mpf_to_u8_bgr": (c_i, [c_p, c_i, c_i, c_p, c_p]),
     "mpf_augment_pairs": (c_i, [ctypes.POINTER(MpfAugmentSample), c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "mpf_photometric_workspace": (c_sz, [c_i]),
+    "mpf_photometric_pairs": (c_i, [ctypes.POINTER(MpfPhotoSample), c_i, c_i, c_i, c_p, c_sz, c_p]),
     "mpf_src_xyz": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
     "mpf_transform_xyz": (c_i, [c_p, c_p, c_i, c_i64, c_p, c_p]),
     "mpf_homography_sample": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),

@@ -6,15 +6,18 @@
 
 What a batch holds is what gen_3dphoto_dynamic.py would have written for the same seed and producer flags (same instance ids, poses,
 renders and hole fill), then RAFT's FlowAugmentor.spatial_transform (resize, stretch, flips, crop; RAFT/core/utils/augmentor.py:67-109)
-and its dataset's packing (RAFT/core/datasets.py:85-90), fused into one mpf_augment_pairs launch per batch.  Photometric augmentation
-(ColorJitter, eraser) stays with the trainer: it works on the returned tensors.
+and its dataset's packing (RAFT/core/datasets.py:85-90), fused into one mpf_augment_pairs launch per batch.  photometric=True (or a dict of
+RAFT_PHOTOMETRIC's keys) adds the photometric half in front of it, as FlowAugmentor.__call__ orders them: ColorJitter (symmetric or
+asymmetric) and the eraser on the full-size u8 frames, bit for bit PIL's arithmetic given the draws (mpf_photometric_pairs); the batch then
+carries batch["photo_meta"].  photometric=None (the default) leaves the batches exactly as they are without it.
 
 Schedule contract (the CLI's, gen_3dphoto_dynamic.py main()): private random.Random(seed) / np.random.RandomState(seed) streams; per
 image with at least one instance in its mask, `pairs_per_image` x (instance id from numpy, dynamic pose, camera pose from `random`);
 images without one draw nothing and are skipped.  Every rank replays the whole schedule and renders the images i with i % world == rank.
 Epoch e+1 continues both streams where epoch e stopped.  shuffle=True: the image order of every epoch is a permutation drawn from a
 third private stream, and the schedule draws are consumed in that processing order.  A fourth private stream picks the samples of a
-batch out of the shuffle buffer (`mix` pairs; 0 = first in, first out) and draws their augmentation parameters.  The batches are a
+batch out of the shuffle buffer (`mix` pairs; 0 = first in, first out) and draws their augmentation parameters.  A fifth one draws the
+photometric parameters, so the spatial draws (flow, valid, meta) are the same with photometric augmentation on or off.  The batches are a
 pure function of the arguments - not of `prefetch`, the fill pool or timing - and state_dict() / load_state_dict() resume them exactly.
 
 The source never touches the global `random`, `np.random` or torch RNGs, nor torch.set_num_threads.
@@ -33,6 +36,10 @@ from . import _lib, host_math, io_formats, ops, pipeline, synth
 from .utils import utils as U
 
 MASK_THRESH = pipeline.MASK_THRESH
+
+# RAFT's FlowAugmentor photometric settings (augmentor.py:32-34, 52): ColorJitter(0.4, 0.4, 0.4, 0.5 / 3.14), asymmetric with probability
+# 0.2, the eraser with probability 0.5 and rectangle extents randint(50, 100)
+RAFT_PHOTOMETRIC = dict(brightness=0.4, contrast=0.4, saturation=0.4, hue=0.5 / 3.14, asymmetric_prob=0.2, eraser_prob=0.5, eraser_bounds=(50, 100))
 
 
 def default_fill_threads():
@@ -115,6 +122,66 @@ def augment_params(rs, H, W, crop, augment):
     return p
 
 
+def photometric_config(photometric):
+    """photometric= of OnlinePairs -> a complete, checked settings dict (None stays None; True = RAFT_PHOTOMETRIC)."""
+    if photometric is None or photometric is False:
+        return None
+    c = dict(RAFT_PHOTOMETRIC)
+    if photometric is not True:
+        unknown = set(photometric) - set(c)
+        if unknown:
+            raise ValueError("photometric: unknown keys %s" % sorted(unknown))
+        c.update(photometric)
+    for k in ("brightness", "contrast", "saturation"):
+        c[k] = float(c[k])
+        if not 0 <= c[k] < float("inf"):
+            raise ValueError("photometric: %s must be a finite value >= 0" % k)
+    c["hue"] = float(c["hue"])
+    if not 0 <= c["hue"] <= 0.5:
+        raise ValueError("photometric: hue must be in [0, 0.5]")
+    for k in ("asymmetric_prob", "eraser_prob"):
+        c[k] = float(c[k])
+        if not 0 <= c[k] <= 1:
+            raise ValueError("photometric: %s must be a probability" % k)
+    lo, hi = (int(v) for v in c["eraser_bounds"])
+    if not 1 <= lo < hi:
+        raise ValueError("photometric: eraser_bounds must be (lo, hi) with 1 <= lo < hi")
+    c["eraser_bounds"] = (lo, hi)
+    return c
+
+
+def jitter_params(rs, c):
+    """One ColorJitter parameter set by torchvision's get_params rules, drawn from the RandomState `rs`: permutation(4), then
+    uniform(max(0, 1 - v), 1 + v) for brightness, contrast and saturation and uniform(-hue, hue), each rounded to float32 (torchvision draws
+    them as float tensors); a setting of 0 is neither drawn nor applied.  -> dict(order (op codes of ops.PHOTO_OPS), brightness, contrast,
+    saturation, hue, hue_shift = int(hue * 255.0)); factors of skipped ops are 1."""
+    perm = [int(v) for v in rs.permutation(4)]
+    p = dict(brightness=1.0, contrast=1.0, saturation=1.0, hue=0.0, hue_shift=0)
+    for k in ("brightness", "contrast", "saturation"):
+        if c[k] > 0:
+            p[k] = float(np.float32(rs.uniform(max(0.0, 1.0 - c[k]), 1.0 + c[k])))
+    if c["hue"] > 0:
+        p["hue"] = float(np.float32(rs.uniform(-c["hue"], c["hue"])))
+        p["hue_shift"] = int(p["hue"] * 255.0)
+    p["order"] = [o for o in perm if c[ops.PHOTO_OPS[o]] > 0]
+    return p
+
+
+def photometric_params(rs, H, W, c):
+    """One sample's photometric draws in RAFT's order (augmentor.py:36-65): asymmetric = rand() < asymmetric_prob, one jitter parameter set
+    (two when asymmetric: image 1's, then image 2's), then the eraser: rand() < eraser_prob, randint(1, 3) rectangles of randint(0, W),
+    randint(0, H), randint(*bounds) x 2 (x0, y0, dx, dy).  -> dict(joint, jitter, rects), the sample format of ops.photometric_pairs."""
+    asym = rs.rand() < c["asymmetric_prob"]
+    jitter = [jitter_params(rs, c) for _ in range(2 if asym else 1)]
+    rects = []
+    if rs.rand() < c["eraser_prob"]:
+        for _ in range(int(rs.randint(1, 3))):
+            x0, y0 = int(rs.randint(0, W)), int(rs.randint(0, H))
+            dx, dy = int(rs.randint(*c["eraser_bounds"])), int(rs.randint(*c["eraser_bounds"]))
+            rects.append((x0, y0, dx, dy))
+    return dict(joint=0 if asym else 1, jitter=jitter, rects=rects)
+
+
 class _Stop(Exception):
     pass
 
@@ -125,12 +192,13 @@ class OnlinePairs:
     base: the CLI's input layout (base/{images,disps,masks}[, mpis]).  crop: (h, w), None = the full frame.  mpi_from: model | npz | disparity;
     ckpt_path: checkpoint or "random:SEED" (model); model_dtype: auto | fp16 (HipPredictor, graph) or fp32 | fp32-mfma | fp64 (PrecisePredictor).
     fill: auto | builtin | peel | none (the CLI's --inpaint; cv2 where installed).  augment: dict of RAFT's FlowAugmentor settings, None = none.
+    photometric: None = none, True = RAFT_PHOTOMETRIC, or a dict of its keys (the rest from RAFT_PHOTOMETRIC).
     mix: shuffle-buffer size in pairs (0 = off).  prefetch: batches enqueued ahead of the consumer.  rank / world_size: default from
     torch.distributed or RANK / WORLD_SIZE.  fill_threads: host threads of fill="builtin" (default: default_fill_threads())."""
 
     def __init__(self, base, batch_size=8, crop=(288, 960), width=1280, height=384, seed=114514, ext_cz=0.15, pairs_per_image=5, poses="v2",
                  mpi_from="model", ckpt_path=None, model_dtype="auto", fill="auto", augment=dict(min_scale=-0.2, max_scale=0.5, do_flip=True),
-                 shuffle=True, mix=32, prefetch=2, rank=None, world_size=None, device=None, planes=64, fill_threads=None):
+                 shuffle=True, mix=32, prefetch=2, rank=None, world_size=None, device=None, planes=64, fill_threads=None, photometric=None):
         if torch.utils.data.get_worker_info() is not None:
             raise RuntimeError("OnlinePairs renders on the GPU in the training process: construct it there, not inside a DataLoader worker")
         if mpi_from not in ("model", "npz", "disparity"):
@@ -143,6 +211,7 @@ class OnlinePairs:
             raise ValueError("crop %s is larger than the %d x %d frame" % (self.crop, self.H, self.W))
         self.seed, self.ext_cz, self.R, self.poses = int(seed), float(ext_cz), int(pairs_per_image), poses
         self.mpi_from, self.augment, self.shuffle, self.mix, self.prefetch = mpi_from, (None if augment is None else dict(augment)), shuffle, int(mix), int(prefetch)
+        self.photometric = photometric_config(photometric)
         if rank is None or world_size is None:
             import torch.distributed as dist
             if dist.is_available() and dist.is_initialized():
@@ -170,10 +239,11 @@ class OnlinePairs:
         self.skipped = []
         self._skipped_names = set()
 
-        # the four private streams and the position: everything state_dict() captures
+        # the four (five with photometric augmentation) private streams and the position: everything state_dict() captures
         self._sched = Schedule(self.seed, self.ext_cz, self.R, poses)
         self._order_rs = np.random.RandomState([self.seed & 0xFFFFFFFF, 2])
         self._aug_rs = np.random.RandomState([self.seed & 0xFFFFFFFF, 1])
+        self._photo_rs = np.random.RandomState([self.seed & 0xFFFFFFFF, 3]) if self.photometric is not None else None
         self._epoch, self._pos, self._order, self._batches = 0, 0, None, 0
         self._buf = []                    # shuffle buffer: dicts(job, r, src, dst, flow, wait)
         self._pending = []                # the pairs of the image rendered last: they join the buffer when the next image has been enqueued
@@ -249,25 +319,32 @@ class OnlinePairs:
 
     # ---- state -------------------------------------------------------------------------------------------------------------------
     def _snapshot(self):
-        return dict(epoch=self._epoch, pos=self._pos, order=None if self._order is None else list(self._order), batches=self._batches,
+        snap = dict(epoch=self._epoch, pos=self._pos, order=None if self._order is None else list(self._order), batches=self._batches,
                     sched=self._sched.state(), order_rs=self._order_rs.get_state(), aug_rs=self._aug_rs.get_state(),
                     buffer=[(e["job"], e["r"]) for e in self._buf + self._pending] if not self._resume_buf else list(self._resume_buf),
                     pending=len(self._pending) if not self._resume_buf else self._resume_pending)
+        if self._photo_rs is not None:
+            snap["photo_rs"] = self._photo_rs.get_state()
+        return snap
 
     def state_dict(self):
-        """The position after the last batch (or epoch end) handed to the consumer: epoch, image position, all four streams and the
-        identities of the pairs waiting in the shuffle buffer (re-rendered on resume)."""
+        """The position after the last batch (or epoch end) handed to the consumer: epoch, image position, all four streams (+ photo_rs, the
+        fifth, with photometric augmentation) and the identities of the pairs waiting in the shuffle buffer (re-rendered on resume)."""
         import copy
         return copy.deepcopy(self._delivered)
 
     def load_state_dict(self, st):
         import copy
+        if self._photo_rs is not None and "photo_rs" not in st:
+            raise ValueError("load_state_dict: this source augments photometrically, the state holds no photo_rs (saved without photometric=)")
         self._stop_producer()
         st = copy.deepcopy(st)
         self._epoch, self._pos, self._order, self._batches = st["epoch"], st["pos"], st["order"], st["batches"]
         self._sched.set_state(st["sched"])
         self._order_rs.set_state(st["order_rs"])
         self._aug_rs.set_state(st["aug_rs"])
+        if self._photo_rs is not None:
+            self._photo_rs.set_state(st["photo_rs"])
         self._buf, self._pending = [], []
         self._resume_buf = [(dict(job), r) for job, r in st["buffer"]]
         self._resume_pending = st["pending"]
@@ -486,7 +563,7 @@ class OnlinePairs:
     # ---- batches -------------------------------------------------------------------------------------------------------------------
     def _batch(self):
         """B entries out of the buffer (uniformly from the augmentation stream when mixing, first in first out otherwise), their augmentation
-        parameters, one mpf_augment_pairs launch.  -> (batch dict, ready event)."""
+        parameters, [one mpf_photometric_pairs launch into scratch frames,] one mpf_augment_pairs launch.  -> (batch dict, ready event)."""
         if self.mix > 0:
             picks = [int(v) for v in self._aug_rs.choice(len(self._buf), self.B, replace=False)]
             taken = [self._buf[j] for j in picks]
@@ -495,17 +572,26 @@ class OnlinePairs:
         else:
             taken, self._buf = self._buf[:self.B], self._buf[self.B:]
         params = [augment_params(self._aug_rs, self.H, self.W, self.crop, self.augment) for _ in taken]
+        photo = None if self._photo_rs is None else [photometric_params(self._photo_rs, self.H, self.W, self.photometric) for _ in taken]
         with torch.cuda.stream(self.stream):
             for e in taken:
                 if e["wait"] is not None:
                     self.stream.wait_event(e["wait"] if isinstance(e["wait"], torch.cuda.Event) else e["wait"].result())
-            samples = [dict(src=e["src"], dst=e["dst"], flow=e["flow"], **p) for e, p in zip(taken, params)]
+            frames = [(e["src"], e["dst"]) for e in taken]
+            if photo is not None:
+                # into scratch frames: the buffer entries stay as rendered (resume re-renders them).  The scratch is allocated on this stream
+                # and consumed on it by the augment launch below, so the allocator does not hand it out again before that launch has run.
+                jit = ops.photometric_pairs([dict(src=s, dst=d, **p) for (s, d), p in zip(frames, photo)])
+                frames = list(zip(jit["src"], jit["dst"]))
+            samples = [dict(src=s, dst=d, flow=e["flow"], **p) for (s, d), e, p in zip(frames, taken, params)]
             out = ops.augment_pairs(samples, size=self.crop)
             ready = torch.cuda.Event()
             ready.record(self.stream)
         self._batches += 1
         out["meta"] = [(e["job"]["name"], e["r"], e["job"]["obj_indices"][e["r"]], p["scale_x"], p["scale_y"], p["flip_h"], p["flip_v"], p["y0"], p["x0"])
                        for e, p in zip(taken, params)]
+        if photo is not None:
+            out["photo_meta"] = photo
         return out, ready
 
     # ---- teardown ------------------------------------------------------------------------------------------------------------------

@@ -491,6 +491,66 @@ def augment_pairs(samples, out=None, size=None):
     return out
 
 
+PHOTO_OPS = ("brightness", "contrast", "saturation", "hue")     # op codes 0..3 of MpfPhotoJitter.order
+
+
+def photometric_pairs(samples, out=None):
+    """RAFT's photometric augmentation (ColorJitter, then the eraser on image 2) of a batch of u8 pairs (mpf_photometric_pairs), on the current
+    stream.  samples: B dicts with src / dst (u8 [H,W,3] BGR on the device), joint (1: one jitter for both frames, one contrast mean over
+    both), jitter (one dict per parameter set - two when joint is 0: order (op names or codes 0..3, applied in that order), brightness,
+    contrast, saturation (factors, default 1), hue_shift (int, default 0)) and rects (up to two (x0, y0, dx, dy)).
+    -> dict(src, dst) u8 [B,H,W,3] BGR; `out` may carry these two tensors."""
+    lib = _lib.load()
+    B = len(samples)
+    if B < 1:
+        raise ValueError("photometric_pairs: no samples")
+    src0 = _dev(samples[0]["src"], "src", torch.uint8)
+    H, W, _ = src0.shape
+    dev = src0.device
+    if out is None:
+        out = dict(src=torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev), dst=torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev))
+    for k in ("src", "dst"):
+        t = out[k]
+        if tuple(t.shape) != (B, H, W, 3) or t.dtype != torch.uint8 or not t.is_contiguous() or t.device != dev:
+            raise ValueError("photometric_pairs: out[%r] must be a contiguous u8 (%d, %d, %d, 3) tensor on %s" % (k, B, H, W, dev))
+    arr = (_lib.MpfPhotoSample * B)()
+    keep = []
+    with torch.cuda.device(dev):
+        for b, s in enumerate(samples):
+            src, dst = _dev(s["src"], "src", torch.uint8), _dev(s["dst"], "dst", torch.uint8)
+            if tuple(src.shape) != (H, W, 3) or tuple(dst.shape) != (H, W, 3):
+                raise ValueError("photometric_pairs: sample %d: src / dst must be [%d,%d,3]" % (b, H, W))
+            keep += [src, dst]
+            a = arr[b]
+            a.src, a.dst, a.src_out, a.dst_out = src.data_ptr(), dst.data_ptr(), out["src"][b].data_ptr(), out["dst"][b].data_ptr()
+            a.joint = int(s.get("joint", 1))
+            jit = list(s.get("jitter", ()))
+            if len(jit) > 2:
+                raise ValueError("photometric_pairs: sample %d: at most two jitter parameter sets" % b)
+            for j, p in enumerate(jit):
+                t = a.jitter[j]
+                order = [PHOTO_OPS.index(o) if isinstance(o, str) else int(o) for o in p.get("order", ())]
+                if len(order) > 4:
+                    raise ValueError("photometric_pairs: sample %d: more than four ops" % b)
+                t.n_ops = len(order)
+                for k, o in enumerate(order):
+                    t.order[k] = o
+                t.brightness, t.contrast, t.saturation = (float(p.get(n, 1.0)) for n in PHOTO_OPS[:3])
+                t.hue_shift = int(p.get("hue_shift", 0))
+            for j in range(len(jit), 2):
+                a.jitter[j].brightness = a.jitter[j].contrast = a.jitter[j].saturation = 1.0
+            rects = list(s.get("rects", ()))
+            if len(rects) > 2:
+                raise ValueError("photometric_pairs: sample %d: at most two rectangles" % b)
+            a.n_rect = len(rects)
+            for k, r in enumerate(rects):
+                for c in range(4):
+                    a.rect[k][c] = int(r[c])
+        ws = torch.empty(int(lib.mpf_photometric_workspace(B)), dtype=torch.uint8, device=dev)
+        _lib.check(lib.mpf_photometric_pairs(arr, B, H, W, _ptr(ws), ws.numel(), _stream()), "mpf_photometric_pairs")
+    return out
+
+
 @_on_device
 def to_u8_bgr(img_3HW):
     lib = _lib.load()

@@ -6,8 +6,11 @@ fast HIP engine, crop 288 x 960, batches of 8, RAFT's default spatial augmentati
   2. beside a synthetic consumer on the caller's stream - a fixed loop of fp32 GEMMs sized to ~20 ms per step - the consumer's step time
      with and without the source feeding it.
 
+With --photometric: the source alone (fill=peel) with RAFT's photometric augmentation off and on (online.RAFT_PHOTOMETRIC), alternated,
+`--rounds` times each (default 2), and the on / off ratio of their medians; nothing else.
+
 Same synthetic KITTI-shaped dataset as tools/bench_cli.py (375 x 1242 PNGs); compare with its "steady state" line for the CLI's rate.
-Usage: bench_online.py [n_images] [--json out.json]"""
+Usage: bench_online.py [n_images] [--json out.json] [--photometric [--rounds N]]"""
 import json
 import os
 import sys
@@ -40,13 +43,13 @@ def dataset(n_img):
     return base
 
 
-def source(base, fill):
+def source(base, fill, photometric=None):
     return OnlinePairs(base, batch_size=8, crop=(288, 960), width=1280, height=384, seed=114514, pairs_per_image=5, mpi_from="model",
-                       ckpt_path="random:0", planes=64, fill=fill, mix=32, prefetch=2)
+                       ckpt_path="random:0", planes=64, fill=fill, mix=32, prefetch=2, photometric=photometric)
 
 
-def alone(base, fill):
-    with source(base, fill) as src:
+def alone(base, fill, photometric=None):
+    with source(base, fill, photometric) as src:
         t0 = time.perf_counter()
         n0 = sum(b["valid"].shape[0] for b in src)                # warm-up epoch: graph capture, first launches, pinned slots
         torch.cuda.synchronize()
@@ -57,7 +60,20 @@ def alone(base, fill):
                 n1 += b["valid"].shape[0]
         torch.cuda.synchronize()
         t2 = time.perf_counter()
-    return dict(fill=fill, warmup_samples=n0, warmup_s=t1 - t0, samples=n1, seconds=t2 - t1, samples_per_s=n1 / (t2 - t1))
+    return dict(fill=fill, photometric=photometric is not None, warmup_samples=n0, warmup_s=t1 - t0, samples=n1, seconds=t2 - t1,
+                samples_per_s=n1 / (t2 - t1))
+
+
+def photometric_ab(base, rounds):
+    runs = {False: [], True: []}
+    for _ in range(rounds):
+        for on in (False, True):
+            r = alone(base, "peel", True if on else None)
+            print(json.dumps(r), flush=True)
+            runs[on].append(r["samples_per_s"])
+    off, on = float(np.median(runs[False])), float(np.median(runs[True]))
+    return dict(fill="peel", rounds=rounds, samples_per_s_off=runs[False], samples_per_s_on=runs[True], median_off=off, median_on=on,
+                ratio_on_off=on / off)
 
 
 def consumer(reps):
@@ -120,6 +136,14 @@ def main():
     n_img = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 24
     out = sys.argv[sys.argv.index("--json") + 1] if "--json" in sys.argv else None
     base = dataset(n_img)
+    if "--photometric" in sys.argv:
+        rounds = int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 2
+        res = dict(images=n_img, pairs_per_epoch=5 * n_img, photometric=photometric_ab(base, rounds))
+        print(json.dumps(res["photometric"]), flush=True)
+        if out:
+            with open(out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     res = dict(images=n_img, pairs_per_epoch=5 * n_img, alone=[], beside=[])
     for fill in ("peel", "builtin"):
         r = alone(base, fill)
