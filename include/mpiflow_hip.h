@@ -271,6 +271,41 @@ typedef struct MpfAugmentSample {
 int mpf_augment_pairs(const MpfAugmentSample *s, int B, int H, int W, int h, int w, float *image1, float *image2, float *flow, float *valid,
                       void *stream);
 
+/* The sparse path of RAFT's loader (its KITTI stage): SparseFlowAugmentor.spatial_transform (RAFT/core/utils/augmentor.py:194-232) with
+ * resize_sparse_flow_map's nearest-pixel scatter (:160-192), after KITTI's 16-bit flow code (writeFlowKITTI -> readFlowKITTI,
+ * core/utils/frame_utils.py:102-120), and the dataset's packing.  Same outputs and layout as mpf_augment_pairs.  One MpfSparseAugmentSample
+ * per sample, in a HOST array of B (device pointers):
+ *   src, dst  u8 [H,W,3] BGR;  flow  f32 [H,W,2];  valid  u8 [H,W], nonzero = valid, NULL = every pixel valid (what writeFlowKITTI writes)
+ *   quantize  1: t = 64.0f*u + 32768.0f in fp32 (each operation rounded), q = trunc(t), u_q = (float)(q - 32768) / 64.0f, the same for v.
+ *             A pixel whose t lies outside -1 < t < 65536 for either component is INVALID: the reference's uint16 cast is undefined
+ *             there, so that rule is this library's.  0: u_q = u, v_q = v.
+ *   resize, scale_x, scale_y, Hr, Wr, flip_h, y0, x0  as MpfAugmentSample (no v-flip); the images take exactly mpf_augment_pairs' path.
+ * Flow and valid per output pixel, (Y, X) = its pixel in the Hr x Wr map after the crop and the flip:
+ *   resize 0: the source pixel (Y, X); valid = its validity; flow (u_q, v_q), 0 where invalid.
+ *   resize 1: the gather form of the scatter.  X < 1 or Y < 1: 0, 0, valid 0 (the scatter never writes row 0 or column 0).  Else the
+ *             candidate rows are {ys : rint((double)ys * scale_y) == Y}, the candidate columns {xs : rint((double)xs * scale_x) == X}
+ *             (rint: half to even, in double); the largest ys with a valid candidate xs, then the largest such xs, wins (numpy's last
+ *             writer in raster order): flow ((float)((double)u_q * scale_x), (float)((double)v_q * scale_y)), valid 1.  No valid candidate:
+ *             0, 0, valid 0 (a hole).
+ *   flip_h negates u after all of this (a hole's 0 becomes -0.0, as RAFT's `flow * [-1.0, 1.0]` does); valid is mirrored, not negated.
+ * -> d_image1, d_image2 f32 [B,3,h,w] RGB;  d_flow f32 [B,2,h,w];  d_valid f32 [B,h,w] (0 / 1).  Validated before anything is launched
+ * (null pointers, B < 1, flags other than 0 / 1, resize == 0 with Hr x Wr != H x W, a scale <= 0, a crop outside the resized frame).
+ * One launch per 32 samples.  Contract in full: mpf_augment_sparse.hip. */
+typedef struct MpfSparseAugmentSample {
+    const uint8_t *src;
+    const uint8_t *dst;
+    const float *flow;
+    const uint8_t *valid;
+    int quantize;
+    int resize;
+    double scale_x, scale_y;
+    int Hr, Wr;
+    int flip_h;
+    int y0, x0;
+} MpfSparseAugmentSample;
+int mpf_augment_sparse_pairs(const MpfSparseAugmentSample *s, int B, int H, int W, int h, int w, float *image1, float *image2, float *flow,
+                             float *valid, void *stream);
+
 /* The photometric half of RAFT's FlowAugmentor (color_transform + eraser_transform, RAFT/core/utils/augmentor.py:36-65), which it runs on the
  * full-size u8 frames before spatial_transform: run it before mpf_augment_pairs, whose src / dst it writes.  One MpfPhotoSample per sample,
  * in a HOST array of B (the pointers in it are device pointers):

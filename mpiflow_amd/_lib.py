@@ -80,6 +80,13 @@ class MpfAugmentSample(ctypes.Structure):
                 ("Hr", c_i), ("Wr", c_i), ("flip_h", c_i), ("flip_v", c_i), ("y0", c_i), ("x0", c_i)]
 
 
+class MpfSparseAugmentSample(ctypes.Structure):
+    """struct MpfSparseAugmentSample of include/mpiflow_hip.h: one sample of mpf_augment_sparse_pairs (device pointers, KITTI code, resize / flip /
+    crop parameters)."""
+    _fields_ = [("src", c_p), ("dst", c_p), ("flow", c_p), ("valid", c_p), ("quantize", c_i), ("resize", c_i), ("scale_x", ctypes.c_double),
+                ("scale_y", ctypes.c_double), ("Hr", c_i), ("Wr", c_i), ("flip_h", c_i), ("y0", c_i), ("x0", c_i)]
+
+
 class MpfPhotoJitter(ctypes.Structure):
     """struct MpfPhotoJitter of include/mpiflow_hip.h: one ColorJitter parameter set of mpf_photometric_pairs."""
     _fields_ = [("n_ops", c_i), ("order", c_i * 4), ("brightness", c_f), ("contrast", c_f), ("saturation", c_f), ("hue_shift", c_i)]
@@ -122,6 +129,7 @@ SIGNATURES = {
     "mpf_stream_probe": (c_i, [c_p, c_p, ctypes.c_size_t, c_i, c_p]),
     "mpf_to_u8_bgr": (c_i, [c_p, c_i, c_i, c_p, c_p]),
     "mpf_augment_pairs": (c_i, [ctypes.POINTER(MpfAugmentSample), c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "mpf_augment_sparse_pairs": (c_i, [ctypes.POINTER(MpfSparseAugmentSample), c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "mpf_photometric_workspace": (c_sz, [c_i]),
     "mpf_photometric_pairs": (c_i, [ctypes.POINTER(MpfPhotoSample), c_i, c_i, c_i, c_p, c_sz, c_p]),
     "mpf_src_xyz": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),

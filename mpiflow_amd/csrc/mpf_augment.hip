@@ -18,7 +18,7 @@
 // B = 8 that is 80 MB written / ~31 MB read per launch: ~14 us at 8 TB/s.  One workgroup = one 256-pixel segment of one output row of one
 // sample; every sample of the launch is in one grid (blockIdx.z).  The sources are read through buffer descriptors sized to the frame, so a
 // tap can never reach past it.
-#include "mpf_common.h"
+#include "mpf_augment_common.h"
 
 namespace {
 
@@ -35,43 +35,6 @@ struct AugDev {                                  // MpfAugmentSample as the kern
 struct AugBatch {
     AugDev s[AUG_MAX_PER_LAUNCH];
 };
-
-struct Tap { int i0, i1; float a; };
-
-// cv2 INTER_LINEAR's source coordinate of destination index d on an axis of n source pixels
-__device__ __forceinline__ Tap lin_tap(int d, int n, double inv)
-{
-    const float f = (float)(((double)d + 0.5) * inv - 0.5);
-    Tap t;
-    if (f < 0.0f) { t.i0 = 0; t.a = 0.0f; }
-    else if (f >= (float)(n - 1)) { t.i0 = n - 1; t.a = 0.0f; }
-    else { t.i0 = (int)floorf(f); t.a = f - (float)t.i0; }
-    t.i1 = min(t.i0 + 1, n - 1);
-    return t;
-}
-
-__device__ __forceinline__ float lerp2(float p00, float p01, float p10, float p11, float ax, float ay)
-{
-    const float bx = 1.0f - ax, by = 1.0f - ay;
-    const float r0 = p00 * bx + p01 * ax;
-    const float r1 = p10 * bx + p11 * ax;
-    return r0 * by + r1 * ay;
-}
-
-__device__ __forceinline__ float to_pixel(float v) { return fminf(fmaxf(rintf(v), 0.0f), 255.0f); }
-
-__device__ __forceinline__ float ld_u8(__amdgpu_buffer_rsrc_t rs, unsigned off)
-{
-    return (float)__builtin_amdgcn_raw_buffer_load_b8(rs, off, 0, 0);
-}
-
-// two dword loads (hipcc pairs them into one buffer_load_dwordx2): a form that took the lanes of __builtin_amdgcn_raw_buffer_load_b64's result
-// read v equal to u on the GPU (tests/test_online.py caught it)
-__device__ __forceinline__ float2 ld_f2(__amdgpu_buffer_rsrc_t rs, unsigned off)
-{
-    return make_float2(__builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0)),
-                       __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, off + 4u, 0, 0)));
-}
 
 __global__ __launch_bounds__(AUG_THREADS) void k_augment_pairs(const AugBatch batch, int H, int W, int h, int w, float *__restrict__ image1,
                                                                float *__restrict__ image2, float *__restrict__ flow_out, float *__restrict__ valid)

@@ -17,7 +17,9 @@ images without one draw nothing and are skipped.  Every rank replays the whole s
 Epoch e+1 continues both streams where epoch e stopped.  shuffle=True: the image order of every epoch is a permutation drawn from a
 third private stream, and the schedule draws are consumed in that processing order.  A fourth private stream picks the samples of a
 batch out of the shuffle buffer (`mix` pairs; 0 = first in, first out) and draws their augmentation parameters.  A fifth one draws the
-photometric parameters, so the spatial draws (flow, valid, meta) are the same with photometric augmentation on or off.  The batches are a
+photometric parameters, so the spatial draws (flow, valid, meta) are the same with photometric augmentation on or off.  sparse=True takes
+RAFT's sparse path instead (SparseFlowAugmentor, its KITTI stage): KITTI's 16-bit flow code, the nearest-pixel flow resize that leaves holes
+(valid = 0), h-flip only and the margin crop, in one mpf_augment_sparse_pairs launch; its draws use the same two streams.  The batches are a
 pure function of the arguments - not of `prefetch`, the fill pool or timing - and state_dict() / load_state_dict() resume them exactly.
 
 The source never touches the global `random`, `np.random` or torch RNGs, nor torch.set_num_threads.
@@ -40,6 +42,12 @@ MASK_THRESH = pipeline.MASK_THRESH
 # RAFT's FlowAugmentor photometric settings (augmentor.py:32-34, 52): ColorJitter(0.4, 0.4, 0.4, 0.5 / 3.14), asymmetric with probability
 # 0.2, the eraser with probability 0.5 and rectangle extents randint(50, 100)
 RAFT_PHOTOMETRIC = dict(brightness=0.4, contrast=0.4, saturation=0.4, hue=0.5 / 3.14, asymmetric_prob=0.2, eraser_prob=0.5, eraser_bounds=(50, 100))
+# RAFT's SparseFlowAugmentor photometric settings (augmentor.py:131-158): ColorJitter(0.3, 0.3, 0.3, 0.3 / 3.14), always symmetric (its
+# color_transform never draws the asymmetric case), the same eraser
+RAFT_SPARSE_PHOTOMETRIC = dict(brightness=0.3, contrast=0.3, saturation=0.3, hue=0.3 / 3.14, asymmetric_prob=0.0, eraser_prob=0.5, eraser_bounds=(50, 100))
+# RAFT's KITTI stage (core/datasets.py:374-378): the sparse augmentor with these settings
+RAFT_KITTI_AUGMENT = dict(min_scale=-0.2, max_scale=0.4, do_flip=False)
+SPARSE_AUGMENT_KEYS = ("min_scale", "max_scale", "do_flip", "spatial_aug_prob")     # what SparseFlowAugmentor.spatial_transform reads
 
 
 def default_fill_threads():
@@ -122,11 +130,56 @@ def augment_params(rs, H, W, crop, augment):
     return p
 
 
-def photometric_config(photometric):
-    """photometric= of OnlinePairs -> a complete, checked settings dict (None stays None; True = RAFT_PHOTOMETRIC)."""
+def sparse_augment_params(rs, H, W, crop, augment):
+    """One sample's parameters by RAFT's SparseFlowAugmentor.spatial_transform rules and order (augmentor.py:194-232), drawn from the
+    RandomState `rs`: s = clip(2**U(min_scale, max_scale), max((h+1)/H, (w+1)/W)) in float64, one scale for both axes; resize with probability
+    spatial_aug_prob (size rint(H*s) x rint(W*s)); h-flip with probability 0.5 when do_flip (no v-flip); y0 = randint(0, Hr-h+20) and
+    x0 = randint(-50, Wr-w+50), always drawn, then clipped to the frame.  augment=None: no resize, no flip, the crop drawn by the same margin
+    rule.  -> the sample dict of ops.augment_sparse_pairs (without the pointers and quantize)."""
+    h, w = crop
+    p = dict(resize=0, scale_x=1.0, scale_y=1.0, Hr=H, Wr=W, flip_h=0, y0=0, x0=0)
+    if augment is not None:
+        a = dict(min_scale=-0.2, max_scale=0.5, do_flip=False, spatial_aug_prob=0.8)
+        a.update(augment)
+        min_scale = np.maximum((h + 1) / float(H), (w + 1) / float(W))
+        scale = float(np.clip(2 ** rs.uniform(a["min_scale"], a["max_scale"]), min_scale, None))
+        if rs.rand() < a["spatial_aug_prob"]:
+            p.update(resize=1, scale_x=scale, scale_y=scale, Hr=int(np.rint(H * scale)), Wr=int(np.rint(W * scale)))
+        if a["do_flip"] and rs.rand() < 0.5:
+            p["flip_h"] = 1
+    if p["Hr"] < h or p["Wr"] < w:
+        raise ValueError("crop %s does not fit the %d x %d frame" % (crop, p["Hr"], p["Wr"]))
+    y0 = int(rs.randint(0, p["Hr"] - h + 20))
+    x0 = int(rs.randint(-50, p["Wr"] - w + 50))
+    p["y0"], p["x0"] = min(max(y0, 0), p["Hr"] - h), min(max(x0, 0), p["Wr"] - w)
+    return p
+
+
+def sparse_config(sparse, augment):
+    """sparse= (and augment=) of OnlinePairs -> dict(quantize) or None (the dense path); checks that augment holds only the keys
+    SparseFlowAugmentor reads (it has no stretch and no v-flip)."""
+    if sparse is None or sparse is False:
+        return None
+    c = dict(quantize=True)
+    if sparse is not True:
+        unknown = set(sparse) - set(c)
+        if unknown:
+            raise ValueError("sparse: unknown keys %s" % sorted(unknown))
+        c.update(sparse)
+    c["quantize"] = bool(c["quantize"])
+    if augment is not None:
+        unknown = set(augment) - set(SPARSE_AUGMENT_KEYS)
+        if unknown:
+            raise ValueError("sparse augmentation reads only %s, not %s" % (", ".join(SPARSE_AUGMENT_KEYS), sorted(unknown)))
+    return c
+
+
+def photometric_config(photometric, sparse=False):
+    """photometric= of OnlinePairs -> a complete, checked settings dict (None stays None; True = RAFT_PHOTOMETRIC, or RAFT_SPARSE_PHOTOMETRIC
+    with sparse, which also refuses an asymmetric_prob > 0)."""
     if photometric is None or photometric is False:
         return None
-    c = dict(RAFT_PHOTOMETRIC)
+    c = dict(RAFT_SPARSE_PHOTOMETRIC if sparse else RAFT_PHOTOMETRIC)
     if photometric is not True:
         unknown = set(photometric) - set(c)
         if unknown:
@@ -147,6 +200,8 @@ def photometric_config(photometric):
     if not 1 <= lo < hi:
         raise ValueError("photometric: eraser_bounds must be (lo, hi) with 1 <= lo < hi")
     c["eraser_bounds"] = (lo, hi)
+    if sparse and c["asymmetric_prob"] > 0:
+        raise ValueError("photometric: the sparse augmentor's colour jitter is always symmetric (asymmetric_prob must be 0)")
     return c
 
 
@@ -167,11 +222,12 @@ def jitter_params(rs, c):
     return p
 
 
-def photometric_params(rs, H, W, c):
+def photometric_params(rs, H, W, c, asymmetric=True):
     """One sample's photometric draws in RAFT's order (augmentor.py:36-65): asymmetric = rand() < asymmetric_prob, one jitter parameter set
     (two when asymmetric: image 1's, then image 2's), then the eraser: rand() < eraser_prob, randint(1, 3) rectangles of randint(0, W),
-    randint(0, H), randint(*bounds) x 2 (x0, y0, dx, dy).  -> dict(joint, jitter, rects), the sample format of ops.photometric_pairs."""
-    asym = rs.rand() < c["asymmetric_prob"]
+    randint(0, H), randint(*bounds) x 2 (x0, y0, dx, dy).  asymmetric=False (SparseFlowAugmentor, augmentor.py:135-158): no asymmetric draw,
+    always symmetric.  -> dict(joint, jitter, rects), the sample format of ops.photometric_pairs."""
+    asym = asymmetric and rs.rand() < c["asymmetric_prob"]
     jitter = [jitter_params(rs, c) for _ in range(2 if asym else 1)]
     rects = []
     if rs.rand() < c["eraser_prob"]:
@@ -193,12 +249,16 @@ class OnlinePairs:
     ckpt_path: checkpoint or "random:SEED" (model); model_dtype: auto | fp16 (HipPredictor, graph) or fp32 | fp32-mfma | fp64 (PrecisePredictor).
     fill: auto | builtin | peel | none (the CLI's --inpaint; cv2 where installed).  augment: dict of RAFT's FlowAugmentor settings, None = none.
     photometric: None = none, True = RAFT_PHOTOMETRIC, or a dict of its keys (the rest from RAFT_PHOTOMETRIC).
+    sparse: None = RAFT's dense FlowAugmentor path; True or dict(quantize=True) = its sparse path (SparseFlowAugmentor, the KITTI stage): the
+    flow through KITTI's 16-bit code (quantize), nearest-pixel flow resize with holes, h-flip only, margin crop; augment= then takes only
+    SPARSE_AUGMENT_KEYS (RAFT_KITTI_AUGMENT is the KITTI stage's), and photometric=True means RAFT_SPARSE_PHOTOMETRIC.
     mix: shuffle-buffer size in pairs (0 = off).  prefetch: batches enqueued ahead of the consumer.  rank / world_size: default from
     torch.distributed or RANK / WORLD_SIZE.  fill_threads: host threads of fill="builtin" (default: default_fill_threads())."""
 
     def __init__(self, base, batch_size=8, crop=(288, 960), width=1280, height=384, seed=114514, ext_cz=0.15, pairs_per_image=5, poses="v2",
                  mpi_from="model", ckpt_path=None, model_dtype="auto", fill="auto", augment=dict(min_scale=-0.2, max_scale=0.5, do_flip=True),
-                 shuffle=True, mix=32, prefetch=2, rank=None, world_size=None, device=None, planes=64, fill_threads=None, photometric=None):
+                 shuffle=True, mix=32, prefetch=2, rank=None, world_size=None, device=None, planes=64, fill_threads=None, photometric=None,
+                 sparse=None):
         if torch.utils.data.get_worker_info() is not None:
             raise RuntimeError("OnlinePairs renders on the GPU in the training process: construct it there, not inside a DataLoader worker")
         if mpi_from not in ("model", "npz", "disparity"):
@@ -211,7 +271,8 @@ class OnlinePairs:
             raise ValueError("crop %s is larger than the %d x %d frame" % (self.crop, self.H, self.W))
         self.seed, self.ext_cz, self.R, self.poses = int(seed), float(ext_cz), int(pairs_per_image), poses
         self.mpi_from, self.augment, self.shuffle, self.mix, self.prefetch = mpi_from, (None if augment is None else dict(augment)), shuffle, int(mix), int(prefetch)
-        self.photometric = photometric_config(photometric)
+        self.sparse = sparse_config(sparse, self.augment)
+        self.photometric = photometric_config(photometric, sparse=self.sparse is not None)
         if rank is None or world_size is None:
             import torch.distributed as dist
             if dist.is_available() and dist.is_initialized():
@@ -563,7 +624,8 @@ class OnlinePairs:
     # ---- batches -------------------------------------------------------------------------------------------------------------------
     def _batch(self):
         """B entries out of the buffer (uniformly from the augmentation stream when mixing, first in first out otherwise), their augmentation
-        parameters, [one mpf_photometric_pairs launch into scratch frames,] one mpf_augment_pairs launch.  -> (batch dict, ready event)."""
+        parameters, [one mpf_photometric_pairs launch into scratch frames,] one mpf_augment_pairs (mpf_augment_sparse_pairs with sparse=) launch.
+        -> (batch dict, ready event)."""
         if self.mix > 0:
             picks = [int(v) for v in self._aug_rs.choice(len(self._buf), self.B, replace=False)]
             taken = [self._buf[j] for j in picks]
@@ -571,8 +633,12 @@ class OnlinePairs:
             self._buf = [e for j, e in enumerate(self._buf) if j not in gone]
         else:
             taken, self._buf = self._buf[:self.B], self._buf[self.B:]
-        params = [augment_params(self._aug_rs, self.H, self.W, self.crop, self.augment) for _ in taken]
-        photo = None if self._photo_rs is None else [photometric_params(self._photo_rs, self.H, self.W, self.photometric) for _ in taken]
+        if self.sparse is None:
+            params = [augment_params(self._aug_rs, self.H, self.W, self.crop, self.augment) for _ in taken]
+        else:
+            params = [sparse_augment_params(self._aug_rs, self.H, self.W, self.crop, self.augment) for _ in taken]
+        photo = None if self._photo_rs is None else [photometric_params(self._photo_rs, self.H, self.W, self.photometric, asymmetric=self.sparse is None)
+                                                     for _ in taken]
         with torch.cuda.stream(self.stream):
             for e in taken:
                 if e["wait"] is not None:
@@ -584,11 +650,14 @@ class OnlinePairs:
                 jit = ops.photometric_pairs([dict(src=s, dst=d, **p) for (s, d), p in zip(frames, photo)])
                 frames = list(zip(jit["src"], jit["dst"]))
             samples = [dict(src=s, dst=d, flow=e["flow"], **p) for (s, d), e, p in zip(frames, taken, params)]
-            out = ops.augment_pairs(samples, size=self.crop)
+            if self.sparse is None:
+                out = ops.augment_pairs(samples, size=self.crop)
+            else:
+                out = ops.augment_sparse_pairs([dict(s, quantize=self.sparse["quantize"]) for s in samples], size=self.crop)
             ready = torch.cuda.Event()
             ready.record(self.stream)
         self._batches += 1
-        out["meta"] = [(e["job"]["name"], e["r"], e["job"]["obj_indices"][e["r"]], p["scale_x"], p["scale_y"], p["flip_h"], p["flip_v"], p["y0"], p["x0"])
+        out["meta"] = [(e["job"]["name"], e["r"], e["job"]["obj_indices"][e["r"]], p["scale_x"], p["scale_y"], p["flip_h"], p.get("flip_v", 0), p["y0"], p["x0"])
                        for e, p in zip(taken, params)]
         if photo is not None:
             out["photo_meta"] = photo

@@ -449,6 +449,21 @@ def png_scanlines(img_HW3_bgr_u8, out=None):
     return out
 
 
+def _augment_out(name, B, H, W, dev, out, size):
+    """The four output tensors of the augmentation launchers: `out`'s (checked), else new ones of crop `size`, else of the frame's size."""
+    if out is not None:
+        h, w = out["valid"].shape[-2:]
+    else:
+        h, w = size if size is not None else (H, W)
+        out = dict(image1=torch.empty((B, 3, h, w), dtype=_f32, device=dev), image2=torch.empty((B, 3, h, w), dtype=_f32, device=dev),
+                   flow=torch.empty((B, 2, h, w), dtype=_f32, device=dev), valid=torch.empty((B, h, w), dtype=_f32, device=dev))
+    for k, shape in (("image1", (B, 3, h, w)), ("image2", (B, 3, h, w)), ("flow", (B, 2, h, w)), ("valid", (B, h, w))):
+        t = out[k]
+        if tuple(t.shape) != shape or t.dtype != _f32 or not t.is_contiguous() or t.device != dev:
+            raise ValueError("%s: out[%r] must be a contiguous fp32 %s tensor on %s" % (name, k, shape, dev))
+    return out, h, w
+
+
 def augment_pairs(samples, out=None, size=None):
     """RAFT's spatial augmentation + tensor packing of a batch of pairs in one launch (mpf_augment_pairs), on the current stream.
     samples: B dicts with src / dst (u8 [H,W,3] BGR) and flow (f32 [H,W,2]) on the device, and resize, scale_x, scale_y, Hr, Wr, flip_h, flip_v,
@@ -461,16 +476,7 @@ def augment_pairs(samples, out=None, size=None):
     src0 = _dev(samples[0]["src"], "src", torch.uint8)
     H, W, _ = src0.shape
     dev = src0.device
-    if out is not None:
-        h, w = out["valid"].shape[-2:]
-    else:
-        h, w = size if size is not None else (H, W)
-        out = dict(image1=torch.empty((B, 3, h, w), dtype=_f32, device=dev), image2=torch.empty((B, 3, h, w), dtype=_f32, device=dev),
-                   flow=torch.empty((B, 2, h, w), dtype=_f32, device=dev), valid=torch.empty((B, h, w), dtype=_f32, device=dev))
-    for k, shape in (("image1", (B, 3, h, w)), ("image2", (B, 3, h, w)), ("flow", (B, 2, h, w)), ("valid", (B, h, w))):
-        t = out[k]
-        if tuple(t.shape) != shape or t.dtype != _f32 or not t.is_contiguous() or t.device != dev:
-            raise ValueError("augment_pairs: out[%r] must be a contiguous fp32 %s tensor on %s" % (k, shape, dev))
+    out, h, w = _augment_out("augment_pairs", B, H, W, dev, out, size)
     arr = (_lib.MpfAugmentSample * B)()
     keep = []
     with torch.cuda.device(dev):
@@ -488,6 +494,45 @@ def augment_pairs(samples, out=None, size=None):
             a.y0, a.x0 = int(s.get("y0", 0)), int(s.get("x0", 0))
         _lib.check(lib.mpf_augment_pairs(arr, B, H, W, h, w, _ptr(out["image1"]), _ptr(out["image2"]), _ptr(out["flow"]), _ptr(out["valid"]), _stream()),
                    "mpf_augment_pairs")
+    return out
+
+
+def augment_sparse_pairs(samples, out=None, size=None):
+    """RAFT's sparse (KITTI-stage) spatial augmentation + tensor packing of a batch of pairs in one launch (mpf_augment_sparse_pairs), on the
+    current stream: KITTI's 16-bit flow code, cv2 INTER_LINEAR images, resize_sparse_flow_map's nearest-pixel flow scatter, h-flip, crop.
+    samples: B dicts with src / dst (u8 [H,W,3] BGR) and flow (f32 [H,W,2]) on the device, optionally valid (u8 or bool [H,W]; missing: every
+    pixel valid), and quantize, resize, scale_x, scale_y, Hr, Wr, flip_h, y0, x0 (missing keys: identity - no KITTI code, no resize, no flip,
+    origin 0).  The crop size is out's, else `size` = (h, w), else the frame's.
+    -> dict(image1, image2 [B,3,h,w] RGB 0..255, flow [B,2,h,w], valid [B,h,w] 0 / 1), all fp32; `out` may carry these four tensors."""
+    lib = _lib.load()
+    B = len(samples)
+    if B < 1:
+        raise ValueError("augment_sparse_pairs: no samples")
+    src0 = _dev(samples[0]["src"], "src", torch.uint8)
+    H, W, _ = src0.shape
+    dev = src0.device
+    out, h, w = _augment_out("augment_sparse_pairs", B, H, W, dev, out, size)
+    arr = (_lib.MpfSparseAugmentSample * B)()
+    keep = []
+    with torch.cuda.device(dev):
+        for b, s in enumerate(samples):
+            src, dst, flow = _dev(s["src"], "src", torch.uint8), _dev(s["dst"], "dst", torch.uint8), _dev(s["flow"], "flow")
+            valid = None if s.get("valid") is None else _dev(s["valid"], "valid", torch.uint8)
+            if tuple(src.shape) != (H, W, 3) or tuple(dst.shape) != (H, W, 3) or tuple(flow.shape) != (H, W, 2):
+                raise ValueError("augment_sparse_pairs: sample %d: src / dst must be [%d,%d,3], flow [%d,%d,2]" % (b, H, W, H, W))
+            if valid is not None and tuple(valid.shape) != (H, W):
+                raise ValueError("augment_sparse_pairs: sample %d: valid must be [%d,%d]" % (b, H, W))
+            keep += [src, dst, flow, valid]
+            a = arr[b]
+            a.src, a.dst, a.flow = src.data_ptr(), dst.data_ptr(), flow.data_ptr()
+            a.valid = None if valid is None else valid.data_ptr()
+            a.quantize, a.resize = int(bool(s.get("quantize", 0))), int(s.get("resize", 0))
+            a.scale_x, a.scale_y = float(s.get("scale_x", 1.0)), float(s.get("scale_y", 1.0))
+            a.Hr, a.Wr = int(s.get("Hr", H)), int(s.get("Wr", W))
+            a.flip_h = int(bool(s.get("flip_h", 0)))
+            a.y0, a.x0 = int(s.get("y0", 0)), int(s.get("x0", 0))
+        _lib.check(lib.mpf_augment_sparse_pairs(arr, B, H, W, h, w, _ptr(out["image1"]), _ptr(out["image2"]), _ptr(out["flow"]), _ptr(out["valid"]),
+                                                _stream()), "mpf_augment_sparse_pairs")
     return out
 
 

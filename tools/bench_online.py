@@ -8,9 +8,11 @@ fast HIP engine, crop 288 x 960, batches of 8, RAFT's default spatial augmentati
 
 With --photometric: the source alone (fill=peel) with RAFT's photometric augmentation off and on (online.RAFT_PHOTOMETRIC), alternated,
 `--rounds` times each (default 2), and the on / off ratio of their medians; nothing else.
+With --sparse: the same A/B between RAFT's dense path (the default augmentation) and its sparse KITTI-stage path
+(sparse=True, augment=online.RAFT_KITTI_AUGMENT), and the sparse / dense ratio of their medians.
 
 Same synthetic KITTI-shaped dataset as tools/bench_cli.py (375 x 1242 PNGs); compare with its "steady state" line for the CLI's rate.
-Usage: bench_online.py [n_images] [--json out.json] [--photometric [--rounds N]]"""
+Usage: bench_online.py [n_images] [--json out.json] [--photometric | --sparse [--rounds N]]"""
 import json
 import os
 import sys
@@ -23,7 +25,7 @@ from PIL import Image
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from mpiflow_amd.online import OnlinePairs  # noqa: E402
+from mpiflow_amd.online import RAFT_KITTI_AUGMENT, OnlinePairs  # noqa: E402
 
 
 def dataset(n_img):
@@ -43,13 +45,14 @@ def dataset(n_img):
     return base
 
 
-def source(base, fill, photometric=None):
+def source(base, fill, photometric=None, sparse=None):
+    kw = dict(sparse=True, augment=RAFT_KITTI_AUGMENT) if sparse else {}
     return OnlinePairs(base, batch_size=8, crop=(288, 960), width=1280, height=384, seed=114514, pairs_per_image=5, mpi_from="model",
-                       ckpt_path="random:0", planes=64, fill=fill, mix=32, prefetch=2, photometric=photometric)
+                       ckpt_path="random:0", planes=64, fill=fill, mix=32, prefetch=2, photometric=photometric, **kw)
 
 
-def alone(base, fill, photometric=None):
-    with source(base, fill, photometric) as src:
+def alone(base, fill, photometric=None, sparse=None):
+    with source(base, fill, photometric, sparse) as src:
         t0 = time.perf_counter()
         n0 = sum(b["valid"].shape[0] for b in src)                # warm-up epoch: graph capture, first launches, pinned slots
         torch.cuda.synchronize()
@@ -60,7 +63,7 @@ def alone(base, fill, photometric=None):
                 n1 += b["valid"].shape[0]
         torch.cuda.synchronize()
         t2 = time.perf_counter()
-    return dict(fill=fill, photometric=photometric is not None, warmup_samples=n0, warmup_s=t1 - t0, samples=n1, seconds=t2 - t1,
+    return dict(fill=fill, photometric=photometric is not None, sparse=bool(sparse), warmup_samples=n0, warmup_s=t1 - t0, samples=n1, seconds=t2 - t1,
                 samples_per_s=n1 / (t2 - t1))
 
 
@@ -74,6 +77,18 @@ def photometric_ab(base, rounds):
     off, on = float(np.median(runs[False])), float(np.median(runs[True]))
     return dict(fill="peel", rounds=rounds, samples_per_s_off=runs[False], samples_per_s_on=runs[True], median_off=off, median_on=on,
                 ratio_on_off=on / off)
+
+
+def sparse_ab(base, rounds):
+    runs = {False: [], True: []}
+    for _ in range(rounds):
+        for on in (False, True):
+            r = alone(base, "peel", sparse=on)
+            print(json.dumps(r), flush=True)
+            runs[on].append(r["samples_per_s"])
+    dense, sparse = float(np.median(runs[False])), float(np.median(runs[True]))
+    return dict(fill="peel", rounds=rounds, samples_per_s_dense=runs[False], samples_per_s_sparse=runs[True], median_dense=dense,
+                median_sparse=sparse, ratio_sparse_dense=sparse / dense)
 
 
 def consumer(reps):
@@ -140,6 +155,14 @@ def main():
         rounds = int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 2
         res = dict(images=n_img, pairs_per_epoch=5 * n_img, photometric=photometric_ab(base, rounds))
         print(json.dumps(res["photometric"]), flush=True)
+        if out:
+            with open(out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
+    if "--sparse" in sys.argv:
+        rounds = int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 2
+        res = dict(images=n_img, pairs_per_epoch=5 * n_img, sparse=sparse_ab(base, rounds))
+        print(json.dumps(res["sparse"]), flush=True)
         if out:
             with open(out, "w") as f:
                 json.dump(res, f, indent=1)
