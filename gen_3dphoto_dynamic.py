@@ -44,7 +44,7 @@ import torch
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-from mpiflow_amd import _lib, host_math, io_formats, ops, pipeline, synth  # noqa: E402
+from mpiflow_amd import io_formats, ops, pipeline, producer  # noqa: E402
 from mpiflow_amd.utils import utils as U  # noqa: E402
 
 
@@ -98,17 +98,6 @@ def parse(argv=None):
                         "415 - every kernel is sized to fill the GPU on its own, a second image in flight finds nothing left to use")
     opt, _ = p.parse_known_args(argv)
     return opt
-
-
-def mpi_from_disparity(image_3HW, disp_HW, S):
-    """Stand-in MPI producer: colours on every plane, sigma = 1e-4 except 50 on the plane nearest to the pixel's
-    disparity (a hard depth assignment).  Returns (mpi [S,4,H,W], disparity [S])."""
-    planes = torch.from_numpy(synth.plane_disparities(S)).to(disp_HW.device)
-    idx = (disp_HW.unsqueeze(0) - planes.view(S, 1, 1)).abs().argmin(0)
-    sigma = torch.full((S,) + tuple(disp_HW.shape), 1e-4, dtype=torch.float32, device=disp_HW.device)
-    sigma.scatter_(0, idx.unsqueeze(0), 50.0)
-    mpi = torch.cat([image_3HW.unsqueeze(0).expand(S, -1, -1, -1), sigma.unsqueeze(1)], dim=1).contiguous()
-    return mpi, planes
 
 
 def outputs_exist(out, name, repeat):
@@ -185,12 +174,9 @@ def main(argv=None):
     # the host side of a pair is a few batched 3x3 / 4x4 matrix operations: intra-op threading only adds fork / join latency to them (and the
     # writer threads want the cores); per-matrix results do not depend on the thread count
     torch.set_num_threads(1)
-    random.seed(opt.seed)                         # gen_3dphoto_dynamic_v2.py:38-39
+    random.seed(opt.seed)                         # gen_3dphoto_dynamic_v2.py:38-39; `sched` below replays these streams privately
     np.random.seed(opt.seed)
-    K = torch.tensor([[0.58, 0, 0.5], [0, 0.58, 0.5], [0, 0, 1]])      # :42-49
-    K[0, :] *= opt.width
-    K[1, :] *= opt.height
-    K = K.unsqueeze(0)
+    sched = producer.Schedule(opt.seed, opt.ext_cz, opt.repeat, opt.poses)
 
     out = opt.out
     if rank == 0:
@@ -208,24 +194,18 @@ def main(argv=None):
         raise SystemExit("gen_3dphoto_dynamic: --model-engine hip computes in fp16 (auto), fp32 or fp64; bf16 is a torch autocast dtype (--model-engine torch)")
     if opt.model_engine == "torch" and opt.model_dtype in ("fp64", "fp32-mfma"):
         raise SystemExit("gen_3dphoto_dynamic: --model-dtype %s is the HIP precise engine's (--model-engine hip)" % opt.model_dtype)
-    precise_dtype = {"fp32": torch.float32, "fp32-mfma": torch.float32, "fp64": torch.float64}.get(opt.model_dtype) if opt.model_engine == "hip" else None
-    if precise_dtype is not None and rank == 0 and opt.mpi_from == "model":
+    if opt.model_engine == "hip" and opt.model_dtype in producer.PRECISE_DTYPES and rank == 0 and opt.mpi_from == "model":
         print("note: --model-engine hip --model-dtype %s selects the PARITY-GRADE producer (mpf_pconv, ~5x the fast engine's time per image, eager launches); "
               "`--model-dtype auto` / fp16 is the fast fp16-storage engine - until round 4 `fp32` named that one (INTEGRATION.md)" % opt.model_dtype, flush=True)
     if opt.mpi_from == "model":                                            # the reference's only producer (:52-60, :92-93)
-        from mpiflow_amd.model import MPIPredictor
-        if opt.ckpt_path.startswith("random:"):
-            model = MPIPredictor(opt.width, opt.height, opt.planes).randomize_(int(opt.ckpt_path.split(":")[1])).eval().to(dev)
-        else:
-            if not os.path.exists(opt.ckpt_path):
-                raise SystemExit("gen_3dphoto_dynamic: checkpoint %r not found.  The reference always runs the AdaMPI network from --ckpt_path "
-                                 "(gen_3dphoto_dynamic_v2.py:52-60); pass the checkpoint, or --ckpt_path random:SEED, or choose another "
-                                 "producer explicitly with --mpi-from npz|disparity." % opt.ckpt_path)
-            model = MPIPredictor.from_checkpoint(opt.ckpt_path, opt.width, opt.height).to(dev)
-            opt.planes = model.num_planes
+        if not opt.ckpt_path.startswith("random:") and not os.path.exists(opt.ckpt_path):
+            raise SystemExit("gen_3dphoto_dynamic: checkpoint %r not found.  The reference always runs the AdaMPI network from --ckpt_path "
+                             "(gen_3dphoto_dynamic_v2.py:52-60); pass the checkpoint, or --ckpt_path random:SEED, or choose another "
+                             "producer explicitly with --mpi-from npz|disparity." % opt.ckpt_path)
+        model = producer.load_model(opt.ckpt_path, opt.width, opt.height, opt.planes, dev)
+        opt.planes = model.num_planes
     elif opt.mpi_from == "disparity" and rank == 0:
         print("WARNING: --mpi-from disparity is a stand-in producer (hard depth assignment), not the reference's AdaMPI network", file=sys.stderr)
-    use_hip_model = model is not None and opt.model_engine == "hip"
     fill_mode = U.resolve_inpaint(opt.inpaint)
     if fill_mode in ("ns", "telea"):
         fill_mode, fill_algo = "builtin", fill_mode
@@ -242,30 +222,6 @@ def main(argv=None):
     else:
         host_fill = None
 
-    class Lane:
-        """Everything one in-flight image owns: its streams, the blended plane stack, the network graph and its static buffers.
-        Built ON the lane's stream, so that the zero-fill of the stack and the packed weights are ordered before its first use."""
-
-        def __init__(self):
-            self.stream, self.tail_stream = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
-            self.stream.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(self.stream):
-                self.renderer = pipeline.PairRenderer(opt.planes, opt.height, opt.width, dev)
-                self.fill_ws = torch.empty(int(_lib.load().mpf_fill_holes_workspace(opt.height, opt.width)), dtype=torch.uint8, device=dev)
-                self.inputs = dict(image=torch.empty((3, opt.height, opt.width), device=dev), disp=torch.empty((opt.height, opt.width), device=dev))
-                self.hip_model = None
-                if use_hip_model and precise_dtype is not None:
-                    from mpiflow_amd.model.precise import PrecisePredictor
-                    self.hip_model = PrecisePredictor(model, dtype=precise_dtype, x3=opt.model_dtype == "fp32")      # the accuracy mode: fp32 / fp64 on mpf_pconv
-                elif use_hip_model:
-                    from mpiflow_amd.model.engine import HipPredictor
-                    self.hip_model = HipPredictor(model, graph=True)
-            self.tail_stream.wait_stream(self.stream)
-
-    lanes = [Lane() for _ in range(max(1, opt.lanes))]
-    dstats = pipeline.DeviceStats(dev)
-    ring = io_formats.OutputRing(opt.height, opt.width, dev, slots=max(4, 2 * max(opt.writers, 1)), threads=max(opt.writers, 1), host_fill=host_fill)
-    t_start = time.perf_counter()
     prof = {}
 
     class lap:                                   # MPIFLOW_PROFILE=1: cumulative host seconds per stage (with a device sync per lap)
@@ -282,6 +238,12 @@ def main(argv=None):
                 if os.environ.get("MPIFLOW_PROFILE") != "host":          # "host": submission time only, no device sync
                     torch.cuda.synchronize()
                 prof[self.key] = prof.get(self.key, 0.0) + time.perf_counter() - self.t
+
+    model_dtype = opt.model_dtype if opt.model_engine == "hip" else None        # None: the torch modules under autocast `amp`
+    lanes = [producer.Lane(dev, opt.height, opt.width, opt.planes, model, model_dtype, amp, lap) for _ in range(max(1, opt.lanes))]
+    dstats = pipeline.DeviceStats(dev)
+    ring = io_formats.OutputRing(opt.height, opt.width, dev, slots=max(4, 2 * max(opt.writers, 1)), threads=max(opt.writers, 1), host_fill=host_fill)
+    t_start = time.perf_counter()
 
     # mask.max() of every image (the instance-id draws need it): decoded once on rank 0 and broadcast; single rank: read off the
     # masks as they are decoded
@@ -327,11 +289,7 @@ def main(argv=None):
                 skipped.append((name, "mask unreadable" if mask_max < 0 else "mask holds no instance (the reference raises here: np.random.randint(0))"))
             continue
         with lap("pose draws"):
-            obj_indices, pose_params = [], []
-            for r in range(opt.repeat):
-                obj_indices.append(np.random.randint(mask_max) + 1)                                                 # :101
-                pose_params.append(host_math.draw_pose_parameters(opt.ext_cz, profile=opt.poses))                     # utils.py:207
-                pose_params.append(host_math.draw_pose_parameters(opt.ext_cz, base_motions=[0, 0, 0], profile=opt.poses))   # :208
+            obj_indices, pose_params = sched.draw(mask_max)
         if not mine:
             continue
         if i in done_before:
@@ -343,7 +301,7 @@ def main(argv=None):
         lane = lanes[n_owned % len(lanes)]
         n_owned += 1
         try:
-            n_new, hand_off = render_image(opt, dev, K, out, name, item, obj_indices, pose_params, lane, model, amp, ring, dstats, fill_mode, lap)
+            n_new, hand_off = render_image(opt, out, name, item, obj_indices, pose_params, lane, ring, dstats, fill_mode, lap)
         except Exception as e:                                             # noqa: BLE001 - isolate the image, keep the batch going
             torch.cuda.synchronize()
             skipped.append((name, "render: %r" % (e,)))
@@ -395,44 +353,16 @@ def main(argv=None):
         dist.destroy_process_group()
 
 
-def render_image(opt, dev, K, out, name, item, obj_indices, pose_params, lane, model, amp, ring, dstats, fill_mode, lap):
-    """One owned image: upload, input stage, MPI producer + blend (once), then `repeat` pairs.  Returns (pairs rendered, hand_off): the pairs are
-    rendered (enqueued) on return; hand_off() enqueues their way out (statistics, scanlines / hole-fill inputs, device->host copies, writer jobs)."""
-    renderer, hip_model, tail_stream, fill_ws = lane.renderer, lane.hip_model, lane.tail_stream, lane.fill_ws
-    H, W = opt.height, opt.width
+def render_image(opt, out, name, item, obj_indices, pose_params, lane, ring, dstats, fill_mode, lap):
+    """One owned image: the lane's front end (upload, input stage, MPI producer + blend, once), its source scanlines to the writers, then
+    `repeat` pairs.  Returns (pairs rendered, hand_off): the pairs are rendered (enqueued) on return; hand_off() enqueues their way out
+    (statistics, scanlines / hole-fill inputs, device->host copies, writer jobs)."""
+    tail_stream, fill_ws = lane.tail_stream, lane.fill_ws
     with torch.cuda.stream(lane.stream):                                  # everything this image enqueues goes to its lane's stream
-        with lap("upload + resize image, disparity"):
-            rgb8 = item["rgb_u8"].to(dev, non_blocking=True)
-            dsp8 = item["disp_u8"].to(dev, non_blocking=True)
-            ids = item["ids_u8"].to(dev, non_blocking=True)
-            if rgb8.shape[:2] == dsp8.shape[:2]:
-                pre = ops.prepare_inputs(rgb_u8=rgb8, disp_u8=dsp8, size=(H, W), out=lane.inputs)     # :82-89 in one launch
-            else:                                                          # files of different sizes: each resized on its own, as :86-89 does
-                pre = dict(image=ops.prepare_inputs(rgb_u8=rgb8, size=(H, W), out=lane.inputs)["image"],
-                           disp=ops.prepare_inputs(disp_u8=dsp8, size=(H, W), out=lane.inputs)["disp"])
-            image, disp = pre["image"][None], pre["disp"][None, None]
-        cum_mask = None
+        front = lane.front(item, npz=os.path.join(opt.base, "mpis", name + ".npz") if opt.mpi_from == "npz" else None)
         with lap("MPI producer + blend"):
-            if opt.mpi_from == "npz":
-                z = np.load(os.path.join(opt.base, "mpis", name + ".npz"))
-                mpi, planes = torch.from_numpy(z["mpi"]).to(dev), torch.from_numpy(z["disparity"]).to(dev)
-            elif hip_model is not None:
-                mpi, cum_mask, planes = hip_model(image, disp)             # static buffers: consumed by blend() below
-            elif model is not None:
-                with torch.no_grad(), torch.autocast("cuda", dtype=amp, enabled=amp is not None):      # :92-93
-                    raw, cm, pd = model(image, disp, raw=True)
-                mpi, cum_mask, planes = raw[0].float().contiguous(), cm[0].float().contiguous(), pd[0].float()
-            else:
-                mpi, planes = mpi_from_disparity(image[0], disp[0, 0], opt.planes)
-            renderer.blend(mpi, image[0], K, planes, cum_mask=cum_mask)      # once per image; the `repeat` pairs below reuse it
-            ring.submit_source(ops.png_scanlines(renderer.src_u8), [os.path.join(out, "src_images", f"{name}_{r}.png") for r in range(opt.repeat)])  # :122
-        poses = host_math.poses_from_parameters(pose_params)               # the image's 2 x repeat poses in one batched evaluation
-        with lap("instance masks"):
-            obj_masks = [ops.prepare_inputs(ids_u8=ids, obj_index=k, size=(H, W))["mask"] for k in obj_indices]      # :102-105
-        with lap("render pairs"):
-            # utils.py:207-208 draws the dynamic pose first; the camera pose renders with obj_mask, the dynamic one with 1 - obj_mask
-            results = renderer.run_pairs(mpi, image[0], K, planes, obj_masks, [(poses[2 * r + 1], poses[2 * r]) for r in range(opt.repeat)],
-                                         cum_mask=cum_mask)
+            ring.submit_source(ops.png_scanlines(lane.renderer.src_u8), [os.path.join(out, "src_images", f"{name}_{r}.png") for r in range(opt.repeat)])  # :122
+        results = lane.pairs(front, obj_indices, pose_params)
         # the tail of the pairs (scanlines / hole-fill hand-off, statistics, copies to the host) runs on a second stream, so it
         # overlaps the next image's network and render - and the HOST enqueues it only after it has submitted the next image's
         # network (main loop): handing five pairs to the writers takes the submitting thread ~1.5 ms, during which the main stream

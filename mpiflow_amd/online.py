@@ -27,14 +27,14 @@ The source never touches the global `random`, `np.random` or torch RNGs, nor tor
 import collections
 import os
 import queue
-import random
 import threading
 
 import numpy as np
 import torch
 import torch.utils.data
 
-from . import _lib, host_math, io_formats, ops, pipeline, synth
+from . import _lib, io_formats, ops, pipeline, producer
+from .producer import Schedule, mpi_from_disparity  # noqa: F401 - online.Schedule / online.mpi_from_disparity
 from .utils import utils as U
 
 MASK_THRESH = pipeline.MASK_THRESH
@@ -59,44 +59,7 @@ def default_fill_threads():
     return max(2, min(32, cores - 4))
 
 
-def mpi_from_disparity(image_3HW, disp_HW, S):
-    """Stand-in MPI producer (the CLI's --mpi-from disparity): colours on every plane, sigma = 1e-4 except 50 on the plane nearest
-    to the pixel's disparity.  Returns (mpi [S,4,H,W], disparity [S])."""
-    planes = torch.from_numpy(synth.plane_disparities(S)).to(disp_HW.device)
-    idx = (disp_HW.unsqueeze(0) - planes.view(S, 1, 1)).abs().argmin(0)
-    sigma = torch.full((S,) + tuple(disp_HW.shape), 1e-4, dtype=torch.float32, device=disp_HW.device)
-    sigma.scatter_(0, idx.unsqueeze(0), 50.0)
-    mpi = torch.cat([image_3HW.unsqueeze(0).expand(S, -1, -1, -1), sigma.unsqueeze(1)], dim=1).contiguous()
-    return mpi, planes
-
-
-# ---- host side: the schedule and the augmentation draws (no GPU) ----------------------------------------------------------------
-
-class Schedule:
-    """The CLI's draw schedule on private streams.  draw(i, mask_max) -> (obj_indices, pose_params) or None (no instance: no draws)."""
-
-    def __init__(self, seed, ext_cz, pairs_per_image, poses="v2"):
-        self.rng = random.Random(seed)
-        self.nrs = np.random.RandomState(seed)
-        self.ext_cz, self.R, self.poses = ext_cz, pairs_per_image, poses
-
-    def draw(self, mask_max):
-        if mask_max <= 0:
-            return None
-        obj_indices, pose_params = [], []
-        for _ in range(self.R):
-            obj_indices.append(int(self.nrs.randint(mask_max)) + 1)                                                         # :101
-            pose_params.append(host_math.draw_pose_parameters(self.ext_cz, rng=self.rng, profile=self.poses))                 # utils.py:207
-            pose_params.append(host_math.draw_pose_parameters(self.ext_cz, base_motions=[0, 0, 0], rng=self.rng, profile=self.poses))   # :208
-        return obj_indices, pose_params
-
-    def state(self):
-        return dict(rng=self.rng.getstate(), nrs=self.nrs.get_state())
-
-    def set_state(self, st):
-        self.rng.setstate(st["rng"])
-        self.nrs.set_state(st["nrs"])
-
+# ---- host side: the augmentation draws (no GPU) -------------------------------------------------------------------------------
 
 def augment_params(rs, H, W, crop, augment):
     """One sample's parameters by RAFT's FlowAugmentor.spatial_transform rules (augmentor.py:67-109), drawn from the RandomState `rs`:
@@ -311,7 +274,6 @@ class OnlinePairs:
         self._resume_buf = []             # (job, r) to re-render before anything else (load_state_dict): the buffer, then the pending pairs
         self._resume_pending = 0
 
-        self._model = self._predictor = None
         self._set_up_gpu(ckpt_path, model_dtype, planes)
         self._producer = None
         self._q = None
@@ -330,44 +292,25 @@ class OnlinePairs:
 
     def _set_up_gpu(self, ckpt_path, model_dtype, planes):
         dev = self.device
-        self.planes = int(planes)
+        self.planes, model = int(planes), None
         with torch.cuda.device(dev):
+            # created in this order, before the network's own streams: the order decides which of them share a hardware queue, and
+            # creating the upload stream last cost the second and later sources of a process 30 % of their rate (tools/bench_online.py)
             self.stream = torch.cuda.Stream(device=dev)              # rendering, fill on the device, augmentation
             self.upload_stream = torch.cuda.Stream(device=dev)       # filled frames of fill="builtin" back to the device
             self.tail = torch.cuda.Stream(device=dev)                # hole fill (peel) / copies of the frames to the host (builtin)
-            self.stream.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(self.stream):
-                if self.mpi_from == "model":
-                    from .model import MPIPredictor
-                    if ckpt_path is None:
-                        raise ValueError("mpi_from='model' needs ckpt_path (a checkpoint, or random:SEED)")
-                    with torch.random.fork_rng(devices=[]):           # module construction draws default initialisations from torch's global RNG
-                        if str(ckpt_path).startswith("random:"):
-                            model = MPIPredictor(self.W, self.H, self.planes).randomize_(int(str(ckpt_path).split(":")[1])).eval().to(dev)
-                        else:
-                            if not os.path.exists(ckpt_path):
-                                raise FileNotFoundError("checkpoint %r not found" % (ckpt_path,))
-                            model = MPIPredictor.from_checkpoint(ckpt_path, self.W, self.H).to(dev)
-                            self.planes = model.num_planes
-                    precise = {"fp32": torch.float32, "fp32-mfma": torch.float32, "fp64": torch.float64}.get(model_dtype)
-                    if precise is not None:
-                        from .model.precise import PrecisePredictor
-                        self._predictor = PrecisePredictor(model, dtype=precise, x3=model_dtype == "fp32")
-                    elif model_dtype in ("auto", "fp16"):
-                        from .model.engine import HipPredictor
-                        self._predictor = HipPredictor(model, graph=True)
-                        # capture the network's graph here, on the constructing thread, not in the producer while other threads use the device
-                        self._predictor(torch.zeros((1, 3, self.H, self.W), device=dev), torch.full((1, 1, self.H, self.W), 0.5, device=dev))
-                    else:
-                        raise ValueError("model_dtype must be auto, fp16, fp32, fp32-mfma or fp64")
-                    self._model = model
-                self.renderer = pipeline.PairRenderer(self.planes, self.H, self.W, dev)
-                self.inputs = dict(image=torch.empty((3, self.H, self.W), device=dev), disp=torch.empty((self.H, self.W), device=dev))
-                self.fill_ws = torch.empty(int(_lib.load().mpf_fill_holes_workspace(self.H, self.W)), dtype=torch.uint8, device=dev)
-            K = torch.tensor([[0.58, 0, 0.5], [0, 0.58, 0.5], [0, 0, 1]])      # gen_3dphoto_dynamic_v2.py:42-49
-            K[0, :] *= self.W
-            K[1, :] *= self.H
-            self.K = K.unsqueeze(0)
+            if self.mpi_from == "model":
+                if ckpt_path is None:
+                    raise ValueError("mpi_from='model' needs ckpt_path (a checkpoint, or random:SEED)")
+                self.stream.wait_stream(torch.cuda.current_stream(dev))
+                with torch.cuda.stream(self.stream):
+                    model = producer.load_model(ckpt_path, self.W, self.H, self.planes, dev)
+                self.planes = model.num_planes
+            self.lane = producer.Lane(dev, self.H, self.W, self.planes, model, model_dtype, streams=(self.stream, self.tail))
+            if model is not None and model_dtype in ("auto", "fp16"):
+                # capture the network's graph here, on the constructing thread, not in the producer while other threads use the device
+                with torch.cuda.stream(self.stream):
+                    self.lane.predictor(torch.zeros((1, 3, self.H, self.W), device=dev), torch.full((1, 1, self.H, self.W), 0.5, device=dev))
         self._pool = None
         self._slots = []
         if self.fill in ("cv2", "builtin"):
@@ -528,36 +471,16 @@ class OnlinePairs:
 
     # ---- rendering -----------------------------------------------------------------------------------------------------------------
     def _render(self, job, item, keep):
-        """One image: upload, input stage, MPI producer + blend, its pairs, hole fill.  -> buffer entries for the pairs r in `keep`."""
-        dev, H, W, ren = self.device, self.H, self.W, self.renderer
+        """One image: the lane's front end (upload, input stage, MPI producer + blend), its pairs, hole fill.  -> buffer entries for the pairs
+        r in `keep`."""
         keep = list(keep)
         with torch.cuda.stream(self.stream):
-            rgb8 = item["rgb_u8"].to(dev, non_blocking=True)
-            dsp8 = item["disp_u8"].to(dev, non_blocking=True)
-            ids = item["ids_u8"].to(dev, non_blocking=True)
-            if rgb8.shape[:2] == dsp8.shape[:2]:
-                pre = ops.prepare_inputs(rgb_u8=rgb8, disp_u8=dsp8, size=(H, W), out=self.inputs)
-            else:
-                pre = dict(image=ops.prepare_inputs(rgb_u8=rgb8, size=(H, W), out=self.inputs)["image"],
-                           disp=ops.prepare_inputs(disp_u8=dsp8, size=(H, W), out=self.inputs)["disp"])
-            image, disp = pre["image"][None], pre["disp"][None, None]
-            cum_mask = None
-            if self.mpi_from == "npz":
-                z = np.load(os.path.join(self.base, "mpis", job["name"] + ".npz"))
-                mpi, planes = torch.from_numpy(z["mpi"]).to(dev), torch.from_numpy(z["disparity"]).to(dev)
-            elif self._predictor is not None:
-                mpi, cum_mask, planes = self._predictor(image, disp)
-            else:
-                mpi, planes = mpi_from_disparity(image[0], disp[0, 0], self.planes)
-            ren.blend(mpi, image[0], self.K, planes, cum_mask=cum_mask)
-            src = ren.src_u8.clone()                                     # the renderer's buffer is the next image's
-            poses = host_math.poses_from_parameters(job["pose_params"])
-            obj_masks = [ops.prepare_inputs(ids_u8=ids, obj_index=k, size=(H, W))["mask"] for k in job["obj_indices"]]
-            results = ren.run_pairs(mpi, image[0], self.K, planes, obj_masks, [(poses[2 * r + 1], poses[2 * r]) for r in range(self.R)],
-                                    cum_mask=cum_mask)
+            front = self.lane.front(item, npz=os.path.join(self.base, "mpis", job["name"] + ".npz") if self.mpi_from == "npz" else None)
+            src = self.lane.renderer.src_u8.clone()                      # the renderer's buffer is the next image's
+            results = self.lane.pairs(front, job["obj_indices"], job["pose_params"])
             rendered = torch.cuda.Event()
             rendered.record(self.stream)
-            dsts = [torch.empty((H, W, 3), dtype=torch.uint8, device=dev) for _ in keep] if self.fill == "peel" else None
+            dsts = [torch.empty((self.H, self.W, 3), dtype=torch.uint8, device=self.device) for _ in keep] if self.fill == "peel" else None
         # the fills run on a second stream, as the CLI's tail stream: the one-workgroup peel kernels / the copies to the host overlap the next
         # image's network instead of running in front of it.  Everything they read or write was allocated on self.stream and stays referenced
         # by the buffer entry until the batch that consumes it has been enqueued behind them (mpf_augment_pairs waits for `filled`).
@@ -568,7 +491,7 @@ class OnlinePairs:
                 res = results[r]
                 e = dict(job=job, r=r, src=src, flow=res["flow_mix"], wait=None, keep=res["slab"])
                 if self.fill == "peel":
-                    e["dst"] = ops.fill_holes(res["frame_mix"], res["fill_mask"], out=dsts[n], workspace=self.fill_ws)
+                    e["dst"] = ops.fill_holes(res["frame_mix"], res["fill_mask"], out=dsts[n], workspace=self.lane.fill_ws)
                 elif self.fill == "none":
                     e["dst"] = res["frame_mix"]
                 else:
@@ -693,7 +616,7 @@ class OnlinePairs:
         self.tail.synchronize()
         self._buf, self._pending, self._resume_buf = [], [], []
         self._free_slots = self._busy_slots = collections.deque()
-        self.renderer = self._predictor = self._model = None
+        self.lane = None
         self._closed = True
 
     def __enter__(self):
