@@ -81,8 +81,9 @@ def parse(argv=None):
                         "convolution on PyTorch/MIOpen (fp32 with --model-dtype fp32 = the reference's CPU numerics, 115 ms per image)")
     p.add_argument("--inpaint", choices=list(U.INPAINT_METHODS), default="auto",
                    help="hole filling of the rendered frame (reference: cv2.inpaint NS radius 3).  auto = cv2 when OpenCV is installed, else "
-                        "builtin = the same algorithm restated in libmpiflow_hip.so, run on the writer threads; peel (alias hip) = the onion-peel "
-                        "GPU kernel, NOT OpenCV's algorithm; none = leave holes white")
+                        "builtin = the same algorithm restated in libmpiflow_hip.so, run on the writer threads; ns-hip = builtin's NS fill on the GPU "
+                        "(the same bytes as builtin, no host fill; parity with cv2 itself unpinned, as for builtin); peel (alias hip) = the "
+                        "onion-peel GPU kernel, NOT OpenCV's algorithm; none = leave holes white")
     p.add_argument("--resume", action="store_true", help="skip images whose outputs (all --repeat pairs) already exist; the RNG schedule is unaffected")
     p.add_argument("--gpus", type=int, default=0,
                    help="GPUs of this node to shard the images over, one process per GPU (the reference's model: scripts/gen_train_kitti15_v2.sh "
@@ -383,7 +384,12 @@ def render_image(opt, out, name, item, obj_indices, pose_params, lane, ring, dst
                     if fill_mode in ("cv2", "builtin"):                    # :284-286 on the host, on a writer thread
                         ring.submit_pair_fill(res["flow_mix"], res["frame_mix"], res["fill_mask"], flo_path, png_path, slab=res.get("slab"))   # one D2H copy per pair
                     else:
-                        frame = ops.fill_holes(res["frame_mix"], res["fill_mask"], workspace=fill_ws) if fill_mode == "peel" else res["frame_mix"]
+                        if fill_mode == "peel":
+                            frame = ops.fill_holes(res["frame_mix"], res["fill_mask"], workspace=fill_ws)
+                        elif fill_mode == "ns-hip":                        # :284-286 on the device, the same bytes as builtin
+                            frame = ops.inpaint_ns(res["frame_mix"], res["fill_mask"], 3, workspace=lane.ns_workspace(1))
+                        else:
+                            frame = res["frame_mix"]
                         ring.submit_pair(res["flow_mix"], ops.png_scanlines(frame), flo_path, png_path)
                     dstats.add(res["flow_mix"], res["fill_mask"])          # statistics only for pairs that went out: n_pairs and the sums stay consistent
                     submitted[0] += 1

@@ -229,6 +229,22 @@ int mpf_fill_holes(uint8_t *d_img, uint8_t *d_hole, int H, int W, void *d_worksp
 #define MPF_INPAINT_TELEA 1
 int mpf_inpaint_host(const uint8_t *img, const uint8_t *mask, int H, int W, int C, double radius, int method, uint8_t *out);
 
+/* The NS branch of mpf_inpaint_host on the GPU, byte for byte: cv2.inpaint(frame_mix, fill_mask, 3, cv2.INPAINT_NS) (utils/utils.py:284-286)
+ * for a batch of B frames.  d_img u8 [B,H,W,3] (BGR, as frame_mix), d_mask u8 [B,H,W] (non-zero = fill) -> d_out u8 [B,H,W,3] (may not
+ * alias the inputs).  The hole pixels of a frame fall into clusters (holes within Chebyshev distance radius + 1 of each other) whose
+ * fast-marching fronts never read each other's pixels; each cluster runs the serial front on one wave (mpf_inpaint_ns.hip).  radius
+ * is rounded and clamped like cvInpaint; 1 - 4 are supported (MPF_ERR_UNSUPPORTED otherwise), as are H, W >= 2 only.  Stream-ordered,
+ * no host synchronisation, no allocation; arguments are validated before any device work.
+ * d_ws: mpf_inpaint_ns_workspace(B, H, W, radius) bytes, about 45 per pixel of the frames padded by one (per padded pixel: flag 1, T 4,
+ * union-find parent 4, cluster list 4, bounding box 16, heap pool 16 - all sized for the worst case of one cluster per hole pixel and a
+ * heap holding every band and hole pixel; ~110 MB for 5 frames of 384 x 1280).
+ * After the call has completed, the first 32-bit words of d_ws hold: [0] clusters, [1] (work counter), [2] heap pool items handed out,
+ * [3] clusters whose heap started in the pool (band > 2048 pixels), [4] clusters whose heap moved to the pool while running,
+ * [5] clusters left unfilled because a bound the fill relies on broke (always 0 unless the kernel is wrong). */
+size_t mpf_inpaint_ns_workspace(int B, int H, int W, double radius);
+int mpf_inpaint_ns(const uint8_t *d_img, const uint8_t *d_mask, int B, int H, int W, double radius, uint8_t *d_out, void *d_ws,
+                   size_t ws_bytes, void *stream);
+
 /* End-of-batch statistics of one pair, without a host round trip: d_out holds
  * MPF_PAIR_STATS_SLICES rows of 4 doubles, one per fixed contiguous slice of the frame:
  * { sum |flow|, hole pixels, max |flow|, max(-flow) } of d_flow_mix [H,W,2] f32 / d_fill_mask [H,W] u8 (empty slices: 0, 0,

@@ -124,6 +124,8 @@ SIGNATURES = {
     "mpf_fill_holes": (c_i, [c_p, c_p, c_i, c_i, c_p, c_sz, c_p]),
     "mpf_prepare_inputs": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
     "mpf_inpaint_host": (c_i, [c_p, c_p, c_i, c_i, c_i, ctypes.c_double, c_i, c_p]),
+    "mpf_inpaint_ns_workspace": (c_sz, [c_i, c_i, c_i, ctypes.c_double]),
+    "mpf_inpaint_ns": (c_i, [c_p, c_p, c_i, c_i, c_i, ctypes.c_double, c_p, c_p, c_sz, c_p]),
     "mpf_png_filter_up": (c_i, [c_p, c_i, c_i, c_p, c_p]),
     "mpf_pair_stats": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p]),
     "mpf_stream_probe": (c_i, [c_p, c_p, ctypes.c_size_t, c_i, c_p]),

@@ -210,7 +210,8 @@ class OnlinePairs:
 
     base: the CLI's input layout (base/{images,disps,masks}[, mpis]).  crop: (h, w), None = the full frame.  mpi_from: model | npz | disparity;
     ckpt_path: checkpoint or "random:SEED" (model); model_dtype: auto | fp16 (HipPredictor, graph) or fp32 | fp32-mfma | fp64 (PrecisePredictor).
-    fill: auto | builtin | peel | none (the CLI's --inpaint; cv2 where installed).  augment: dict of RAFT's FlowAugmentor settings, None = none.
+    fill: auto | builtin | ns-hip | peel | none (the CLI's --inpaint; cv2 where installed).  ns-hip: builtin's NS fill on the GPU, the same bytes
+    as builtin without the host threads (one batched call per image's pairs on the tail stream); parity with cv2 itself is unpinned, as for builtin.  augment: dict of RAFT's FlowAugmentor settings, None = none.
     photometric: None = none, True = RAFT_PHOTOMETRIC, or a dict of its keys (the rest from RAFT_PHOTOMETRIC).
     sparse: None = RAFT's dense FlowAugmentor path; True or dict(quantize=True) = its sparse path (SparseFlowAugmentor, the KITTI stage): the
     flow through KITTI's 16-bit code (quantize), nearest-pixel flow resize with holes, h-flip only, margin crop; augment= then takes only
@@ -252,8 +253,8 @@ class OnlinePairs:
             raise _lib.MpiFlowHipError("OnlinePairs renders with the HIP kernels of mpiflow_amd: device must be a GPU")
         _lib.load()
         fm = U.resolve_inpaint(fill)
-        if fm not in ("cv2", "builtin", "peel", "none"):
-            raise ValueError("fill must be auto, builtin, peel or none")
+        if fm not in ("cv2", "builtin", "ns-hip", "peel", "none"):
+            raise ValueError("fill must be auto, builtin, ns-hip, peel or none")
         self.fill = fm
         self.fill_threads = int(fill_threads) if fill_threads else default_fill_threads()
 
@@ -298,7 +299,7 @@ class OnlinePairs:
             # creating the upload stream last cost the second and later sources of a process 30 % of their rate (tools/bench_online.py)
             self.stream = torch.cuda.Stream(device=dev)              # rendering, fill on the device, augmentation
             self.upload_stream = torch.cuda.Stream(device=dev)       # filled frames of fill="builtin" back to the device
-            self.tail = torch.cuda.Stream(device=dev)                # hole fill (peel) / copies of the frames to the host (builtin)
+            self.tail = torch.cuda.Stream(device=dev)                # hole fill (peel, ns-hip) / copies of the frames to the host (builtin)
             if self.mpi_from == "model":
                 if ckpt_path is None:
                     raise ValueError("mpi_from='model' needs ckpt_path (a checkpoint, or random:SEED)")
@@ -481,23 +482,31 @@ class OnlinePairs:
             rendered = torch.cuda.Event()
             rendered.record(self.stream)
             dsts = [torch.empty((self.H, self.W, 3), dtype=torch.uint8, device=self.device) for _ in keep] if self.fill == "peel" else None
+            if self.fill == "ns-hip" and keep:
+                dsts = torch.empty((len(keep), self.H, self.W, 3), dtype=torch.uint8, device=self.device)
         # the fills run on a second stream, as the CLI's tail stream: the one-workgroup peel kernels / the copies to the host overlap the next
         # image's network instead of running in front of it.  Everything they read or write was allocated on self.stream and stays referenced
         # by the buffer entry until the batch that consumes it has been enqueued behind them (mpf_augment_pairs waits for `filled`).
         self.tail.wait_event(rendered)
         out = []
         with torch.cuda.stream(self.tail):
+            if self.fill == "ns-hip" and keep:                           # the image's pairs in one call: one serial front per hole cluster
+                frames = torch.stack([results[r]["frame_mix"] for r in keep])
+                holes = torch.stack([results[r]["fill_mask"] for r in keep])
+                ops.inpaint_ns(frames, holes, 3, out=dsts, workspace=self.lane.ns_workspace(len(keep)))
             for n, r in enumerate(keep):
                 res = results[r]
                 e = dict(job=job, r=r, src=src, flow=res["flow_mix"], wait=None, keep=res["slab"])
                 if self.fill == "peel":
                     e["dst"] = ops.fill_holes(res["frame_mix"], res["fill_mask"], out=dsts[n], workspace=self.lane.fill_ws)
+                elif self.fill == "ns-hip":
+                    e["dst"] = dsts[n]
                 elif self.fill == "none":
                     e["dst"] = res["frame_mix"]
                 else:
                     e["dst"], e["wait"] = self._host_fill(res["frame_mix"], res["fill_mask"])
                 out.append(e)
-            if self.fill in ("peel", "none"):
+            if self.fill in ("peel", "ns-hip", "none"):
                 filled = torch.cuda.Event()
                 filled.record(self.tail)
                 for e in out:

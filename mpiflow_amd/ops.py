@@ -422,6 +422,47 @@ def inpaint_host(img_u8, mask_u8, radius=3, method=INPAINT_NS, out=None):
     return out
 
 
+@_on_device
+def inpaint_ns(img, mask, radius=3, out=None, workspace=None):
+    """inpaint_host(img, mask, radius, INPAINT_NS) on the GPU, byte for byte (mpf_inpaint_ns): the reference's
+    cv2.inpaint(frame_mix, fill_mask, 3, cv2.INPAINT_NS) (utils/utils.py:284-286), as restated by mpf_inpaint_host; parity with
+    cv2 itself is as unpinned as the host restatement's.  img u8 [H,W,3] or [B,H,W,3] (BGR), mask [H,W] or [B,H,W] (non-zero = fill),
+    both on the device; radius 1 - 4 (after cvInpaint's rounding); H, W >= 2.  Stream-ordered on the current stream, no host
+    synchronisation.  Returns `out` (a new tensor unless given; it may not alias `img`).  `workspace`: u8 device tensor of at least
+    inpaint_ns_workspace(B, H, W) bytes, allocated per call when absent or short."""
+    lib = _lib.load()
+    src = _dev(img, "img", torch.uint8)
+    if src.dim() not in (3, 4) or src.shape[-1] != 3:
+        raise ValueError("inpaint_ns: img must be [H,W,3] or [B,H,W,3] (got %s)" % (tuple(src.shape),))
+    B, H, W = (1,) + tuple(src.shape[:2]) if src.dim() == 3 else tuple(src.shape[:3])
+    m = _dev(mask, "mask", torch.uint8)
+    if m.numel() != B * H * W:
+        raise ValueError("inpaint_ns: mask of %s for images of %s" % (tuple(m.shape), tuple(src.shape)))
+    if out is None:
+        out = torch.empty_like(src)
+    elif out.shape != src.shape or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != src.device:
+        raise ValueError("inpaint_ns: out must be a contiguous u8 tensor of %s on %s" % (tuple(src.shape), src.device))
+    need = inpaint_ns_workspace(B, H, W, radius)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=src.device)
+    _lib.check(lib.mpf_inpaint_ns(_ptr(src), _ptr(m), B, H, W, float(radius), _ptr(out), _ptr(workspace), int(workspace.numel()), _stream()),
+               "mpf_inpaint_ns")
+    return out
+
+
+def inpaint_ns_workspace(B, H, W, radius=3):
+    """bytes of workspace mpf_inpaint_ns needs for B frames of H x W (about 45 per pixel: include/mpiflow_hip.h)"""
+    return int(_lib.load().mpf_inpaint_ns_workspace(int(B), int(H), int(W), float(radius)))
+
+
+def inpaint_ns_counters(workspace):
+    """What the last inpaint_ns call with this workspace did, read from its first words once it has completed (synchronises with the
+    current stream): clusters, heap pool items, clusters whose heap started in / moved to the pool, and `failed` - clusters left
+    unfilled because a bound the fill relies on broke (0 unless the kernel is wrong)."""
+    w = workspace[:24].view(torch.int32).cpu().tolist()
+    return dict(clusters=w[0], pool_items=w[2], spilled_at_start=w[3], spilled_running=w[4], failed=w[5])
+
+
 PAIR_STATS_SLICES = 64          # MPF_PAIR_STATS_SLICES
 
 

@@ -102,9 +102,17 @@ class Lane:
         with torch.cuda.stream(self.stream):
             self.renderer = pipeline.PairRenderer(planes, H, W, device)
             self.fill_ws = torch.empty(int(_lib.load().mpf_fill_holes_workspace(H, W)), dtype=torch.uint8, device=device)
+            self.ns_ws = None                                     # fill "ns-hip": sized by its first use (ns_workspace)
             self.inputs = dict(image=torch.empty((3, H, W), device=device), disp=torch.empty((H, W), device=device))
             self.predictor = make_predictor(model, model_dtype) if model is not None and model_dtype is not None else None
         self.tail_stream.wait_stream(self.stream)
+
+    def ns_workspace(self, B):
+        """The workspace of fill "ns-hip" (ops.inpaint_ns) for B frames: allocated on the current stream at first use, grown when short."""
+        need = ops.inpaint_ns_workspace(B, self.H, self.W)
+        if self.ns_ws is None or self.ns_ws.numel() < need:
+            self.ns_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self.ns_ws
 
     def front(self, item, npz=None):
         """item (io_formats.InputPrefetcher's): upload, input stage (:82-89), MPI producer - the stack in the file `npz` if given, else the

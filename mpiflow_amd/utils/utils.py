@@ -57,7 +57,7 @@ def have_cv2():
         return False
 
 
-INPAINT_METHODS = ("auto", "cv2", "builtin", "ns", "telea", "peel", "hip", "none")
+INPAINT_METHODS = ("auto", "cv2", "builtin", "ns", "telea", "ns-hip", "peel", "hip", "none")
 
 
 def resolve_inpaint(method):
@@ -76,6 +76,8 @@ def _inpaint(frame_dev, hole_dev, method, algo="ns"):
       'cv2'      the reference's own call (third-party; needs OpenCV)
       'builtin'  that algorithm as restated in libmpiflow_hip.so (mpf_inpaint_host; on the host, like the reference's call);
                  'ns' / 'telea' force one of the two
+      'ns-hip'   the NS branch of 'builtin' on the GPU (mpf_inpaint_ns): the same bytes as 'builtin' with algo 'ns'; parity with cv2
+                 itself stays as unpinned as 'builtin''s.  NS only: algo 'telea' raises
       'peel' (alias 'hip')  the onion-peel GPU kernel - NOT OpenCV's algorithm, an explicit opt-in only
       'none'     leave the holes as they are."""
     method = resolve_inpaint(method)
@@ -87,6 +89,10 @@ def _inpaint(frame_dev, hole_dev, method, algo="ns"):
                            cv2.INPAINT_TELEA if algo == "telea" else cv2.INPAINT_NS)
     if method == "builtin":
         return ops.inpaint_host(frame_dev.cpu().numpy(), hole_dev.cpu().numpy(), 3, ops.INPAINT_TELEA if algo == "telea" else ops.INPAINT_NS)
+    if method == "ns-hip":
+        if algo == "telea":
+            raise ValueError("inpaint 'ns-hip' is OpenCV's NS fill on the GPU; Telea (algo='telea') runs on the host only ('builtin' / 'cv2')")
+        return ops.inpaint_ns(frame_dev, hole_dev).cpu().numpy()
     if method == "peel":
         return ops.fill_holes(frame_dev, hole_dev).cpu().numpy()
     return frame_dev.cpu().numpy()

@@ -12,7 +12,8 @@ With --sparse: the same A/B between RAFT's dense path (the default augmentation)
 (sparse=True, augment=online.RAFT_KITTI_AUGMENT), and the sparse / dense ratio of their medians.
 
 Same synthetic KITTI-shaped dataset as tools/bench_cli.py (375 x 1242 PNGs); compare with its "steady state" line for the CLI's rate.
-Usage: bench_online.py [n_images] [--json out.json] [--photometric | --sparse [--rounds N]]"""
+With --fill a,b,...: parts 1 and 2 for those fill methods, in that order (default peel,builtin; ns-hip = the GPU NS fill); --alone-only skips part 2.
+Usage: bench_online.py [n_images] [--json out.json] [--photometric | --sparse [--rounds N] | --fill LIST [--alone-only]]"""
 import json
 import os
 import sys
@@ -167,12 +168,15 @@ def main():
             with open(out, "w") as f:
                 json.dump(res, f, indent=1)
         return
+    fills = sys.argv[sys.argv.index("--fill") + 1].split(",") if "--fill" in sys.argv else ["peel", "builtin"]
     res = dict(images=n_img, pairs_per_epoch=5 * n_img, alone=[], beside=[])
-    for fill in ("peel", "builtin"):
+    for fill in fills:
         r = alone(base, fill)
         print(json.dumps(r), flush=True)
         res["alone"].append(r)
-    for fill in ("peel", "builtin"):
+    if "--alone-only" in sys.argv:
+        fills = []
+    for fill in fills:
         r = beside(base, fill)
         print(json.dumps(r), flush=True)
         res["beside"].append(r)
