@@ -358,6 +358,42 @@ typedef struct MpfPhotoSample {
 size_t mpf_photometric_workspace(int B);
 int mpf_photometric_pairs(const MpfPhotoSample *s, int B, int H, int W, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* RAFT's on-demand correlation lookup (RAFT/alt_cuda_corr, called by AlternateCorrBlock, RAFT/core/corr.py:63-91): the 81 * L window of
+ * correlations around each query pixel's current match, from the two feature maps, without the all-pairs volume.  All maps channel-last:
+ *   fmap1   f32 [B,H,W,C];  f2[i]  f32 [B,Hl[i],Wl[i],C], level i of fmap2's average-pooled pyramid (i < levels);  coords  f32 [B,2,H,W],
+ *   (x, y) in pixels of level 0;  rd = 2 * radius + 1
+ *   out[b, i*rd*rd + a*rd + c, y, x] = scale * sum_ch fmap1[b,y,x,ch] * bilinear(f2[i][b,:,:,ch], X, Y),
+ *       X = coords[b,0,y,x] / 2^i + (a - radius),  Y = coords[b,1,y,x] / 2^i + (c - radius)      (the FIRST window index moves x, as RAFT's does)
+ *   bilinear: the four integer taps around (floor X, floor Y), a tap outside the level contributes 0 (grid_sample, align_corners, zero padding).
+ *   Evaluated as RAFT's kernel does: the (rd+1)^2 dot products on the integer grid around (floor x, floor y), then the four-tap blend of those.
+ * coords are UNTRUSTED: any value is legal.  A coordinate that is NaN, +-inf, or so far out that no tap can lie in the level puts every tap of
+ * that pixel and level outside: its outputs are exactly 0 and it adds nothing to any gradient.  (It is clamped in floating point before the
+ * conversion to int; no value of coords makes the kernels touch memory outside the buffers.)
+ * mpf_corr_lookup           writes out f32 [B, levels*rd*rd, H, W]; one launch for all levels.
+ * mpf_corr_lookup_backward  reads out as the cotangent [B, levels*rd*rd, H, W]; WRITES grad_fmap1 f32 [B,H,W,C] (a per-pixel sum: bit-identical
+ *                           from run to run) and ADDS into grad_f2[i] f32 [B,Hl[i],Wl[i],C] with fp32 atomics (the caller zeroes them; sums
+ *                           differ in the last bits from run to run).  No gradient for coords (RAFT detaches them before every lookup).
+ * fp32 throughout.  C a multiple of 32; radius 1..8; levels 1..MPF_CORR_MAX_LEVELS; every level at least 2 x 2 (H, W >= 2^levels for a pooled
+ * pyramid: below that the reference's own sampler divides by zero); maps 16-byte aligned; every map below 2^31 elements.  Validated before
+ * anything is launched.  plain = 1 selects the first form of the forward kernel (one thread per output entry, four gathered taps, no sharing):
+ * kept as the same-box yardstick of tools/bench_corr.py and as a cross-check in the tests; same contract, same results up to rounding. */
+#define MPF_CORR_MAX_LEVELS 6
+typedef struct MpfCorrArgs {
+    const float *fmap1;
+    const float *f2[MPF_CORR_MAX_LEVELS];
+    const float *coords;
+    float *out;                              /* forward: written;  backward: the cotangent, read */
+    float *grad_fmap1;                       /* backward only */
+    float *grad_f2[MPF_CORR_MAX_LEVELS];     /* backward only */
+    int B, C, H, W;
+    int Hl[MPF_CORR_MAX_LEVELS], Wl[MPF_CORR_MAX_LEVELS];
+    int radius, levels;
+    float scale;                             /* RAFT: 1 / sqrt(C) */
+    int plain;
+} MpfCorrArgs;
+int mpf_corr_lookup(const MpfCorrArgs *a, void *stream);
+int mpf_corr_lookup_backward(const MpfCorrArgs *a, void *stream);
+
 /* [3,H,W] float RGB -> [H,W,3] u8 BGR, clip(rint(x*255))  (utils/utils.py:174-177) */
 int mpf_to_u8_bgr(const float *d_img, int H, int W, uint8_t *d_out, void *stream);
 

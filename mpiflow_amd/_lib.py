@@ -98,6 +98,16 @@ class MpfPhotoSample(ctypes.Structure):
                 ("rect", (c_i * 4) * 2)]
 
 
+CORR_MAX_LEVELS = 6     # MPF_CORR_MAX_LEVELS
+
+
+class MpfCorrArgs(ctypes.Structure):
+    """struct MpfCorrArgs of include/mpiflow_hip.h: RAFT's on-demand correlation lookup and its gradient (device pointers, channel-last maps)."""
+    _fields_ = [("fmap1", c_p), ("f2", c_p * CORR_MAX_LEVELS), ("coords", c_p), ("out", c_p), ("grad_fmap1", c_p), ("grad_f2", c_p * CORR_MAX_LEVELS),
+                ("B", c_i), ("C", c_i), ("H", c_i), ("W", c_i), ("Hl", c_i * CORR_MAX_LEVELS), ("Wl", c_i * CORR_MAX_LEVELS),
+                ("radius", c_i), ("levels", c_i), ("scale", c_f), ("plain", c_i)]
+
+
 MAX_VIEWS = 16          # MPF_MAX_VIEWS
 
 # name -> (restype, argtypes); must list every symbol include/mpiflow_hip.h declares (tests/test_capi.py checks)
@@ -134,6 +144,8 @@ SIGNATURES = {
     "mpf_augment_sparse_pairs": (c_i, [ctypes.POINTER(MpfSparseAugmentSample), c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "mpf_photometric_workspace": (c_sz, [c_i]),
     "mpf_photometric_pairs": (c_i, [ctypes.POINTER(MpfPhotoSample), c_i, c_i, c_i, c_p, c_sz, c_p]),
+    "mpf_corr_lookup": (c_i, [ctypes.POINTER(MpfCorrArgs), c_p]),
+    "mpf_corr_lookup_backward": (c_i, [ctypes.POINTER(MpfCorrArgs), c_p]),
     "mpf_src_xyz": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
     "mpf_transform_xyz": (c_i, [c_p, c_p, c_i, c_i64, c_p, c_p]),
     "mpf_homography_sample": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),

@@ -637,6 +637,83 @@ def photometric_pairs(samples, out=None):
     return out
 
 
+def _corr_tensor(t, name, ndim):
+    """RAFT's correlation lookup takes its tensors as they are: no silent copy, cast or move."""
+    if not isinstance(t, torch.Tensor):
+        raise _lib.MpiFlowHipError("corr_lookup: %s must be a torch.Tensor (got %s)" % (name, type(t).__name__))
+    if not t.is_cuda:
+        raise _lib.MpiFlowHipError("corr_lookup: %s must live on the GPU (got %s); mpiflow_amd has no CPU path" % (name, t.device))
+    if t.dtype != _f32:
+        raise _lib.MpiFlowHipError("corr_lookup: %s must be float32 (got %s)" % (name, t.dtype))
+    if t.dim() != ndim:
+        raise _lib.MpiFlowHipError("corr_lookup: %s must have %d dimensions (got shape %s)" % (name, ndim, tuple(t.shape)))
+    if not t.is_contiguous():
+        raise _lib.MpiFlowHipError("corr_lookup: %s must be contiguous" % name)
+    return t
+
+
+def _corr_args(fmap1_nhwc, f2_levels_nhwc, coords, radius, scale, plain=False):
+    f1 = _corr_tensor(fmap1_nhwc, "fmap1_nhwc", 4)
+    B, H, W, C = f1.shape
+    levels = list(f2_levels_nhwc)
+    if not 1 <= len(levels) <= _lib.CORR_MAX_LEVELS:
+        raise _lib.MpiFlowHipError("corr_lookup: num_levels must be 1..%d (got %d)" % (_lib.CORR_MAX_LEVELS, len(levels)))
+    co = _corr_tensor(coords, "coords", 4)
+    if tuple(co.shape) != (B, 2, H, W):
+        raise _lib.MpiFlowHipError("corr_lookup: coords must be [B,2,H,W] = %s (got %s)" % ((B, 2, H, W), tuple(co.shape)))
+    a = _lib.MpfCorrArgs()
+    a.fmap1, a.coords = f1.data_ptr(), co.data_ptr()
+    a.B, a.C, a.H, a.W = B, C, H, W
+    for i, t in enumerate(levels):
+        t = _corr_tensor(t, "f2_levels_nhwc[%d]" % i, 4)
+        if t.shape[0] != B or t.shape[3] != C or t.device != f1.device:
+            raise _lib.MpiFlowHipError("corr_lookup: f2_levels_nhwc[%d] is %s on %s for fmap1_nhwc %s on %s" % (i, tuple(t.shape), t.device, tuple(f1.shape), f1.device))
+        a.f2[i], a.Hl[i], a.Wl[i] = t.data_ptr(), t.shape[1], t.shape[2]
+    a.radius, a.levels = int(radius), len(levels)
+    a.scale = 1.0 / float(torch.sqrt(torch.tensor(C).float())) if scale is None else float(scale)       # RAFT divides by the fp32 sqrt(C)
+    a.plain = int(bool(plain))
+    return a, levels
+
+
+@_on_device
+def corr_lookup(fmap1_nhwc, f2_levels_nhwc, coords, radius, out=None, scale=None, plain=False):
+    """mpf_corr_lookup: RAFT's on-demand correlation lookup (AlternateCorrBlock / alt_cuda_corr), every level in one launch.
+    fmap1_nhwc [B,H,W,C], f2_levels_nhwc: level i of fmap2's avg_pool2d pyramid as [B,H_i,W_i,C], coords [B,2,H,W] (x, y; any value is
+    legal, non-finite ones give 0) -> [B, L*(2r+1)^2, H, W], scaled by `scale` (default 1/sqrt(C)).  float32, contiguous, on the GPU, or
+    MpiFlowHipError.  `plain`: the one-thread-per-entry form of the kernel (yardstick of tools/bench_corr.py).  Asynchronous on the current stream."""
+    lib = _lib.load()
+    a, levels = _corr_args(fmap1_nhwc, f2_levels_nhwc, coords, radius, scale, plain)
+    rd = 2 * int(radius) + 1
+    shape = (a.B, len(levels) * rd * rd, a.H, a.W)
+    if out is None:
+        out = torch.empty(shape, dtype=_f32, device=fmap1_nhwc.device)
+    elif tuple(_corr_tensor(out, "out", 4).shape) != shape or out.device != fmap1_nhwc.device:
+        raise _lib.MpiFlowHipError("corr_lookup: out must be %s on %s" % (shape, fmap1_nhwc.device))
+    a.out = out.data_ptr()
+    _lib.check(lib.mpf_corr_lookup(ctypes.byref(a), _stream()), "mpf_corr_lookup")
+    return out
+
+
+@_on_device
+def corr_lookup_backward(fmap1_nhwc, f2_levels_nhwc, coords, grad_out, radius, scale=None):
+    """mpf_corr_lookup_backward: the cotangent grad_out [B, L*(2r+1)^2, H, W] of corr_lookup -> (grad_fmap1_nhwc, [grad_f2_i_nhwc per level]).
+    grad_fmap1 is a per-pixel sum (bit-identical from run to run); the levels' gradients are scattered with fp32 atomics (last bits vary).
+    There is no gradient for coords.  Asynchronous on the current stream."""
+    lib = _lib.load()
+    a, levels = _corr_args(fmap1_nhwc, f2_levels_nhwc, coords, radius, scale)
+    rd = 2 * int(radius) + 1
+    shape = (a.B, len(levels) * rd * rd, a.H, a.W)
+    if tuple(_corr_tensor(grad_out, "grad_out", 4).shape) != shape:
+        raise _lib.MpiFlowHipError("corr_lookup_backward: grad_out must be %s (got %s)" % (shape, tuple(grad_out.shape)))
+    g1 = torch.empty_like(fmap1_nhwc)
+    g2 = [torch.zeros_like(t) for t in levels]
+    a.out, a.grad_fmap1 = grad_out.data_ptr(), g1.data_ptr()
+    for i, t in enumerate(g2):
+        a.grad_f2[i] = t.data_ptr()
+    _lib.check(lib.mpf_corr_lookup_backward(ctypes.byref(a), _stream()), "mpf_corr_lookup_backward")
+    return g1, g2
+
+
 @_on_device
 def to_u8_bgr(img_3HW):
     lib = _lib.load()

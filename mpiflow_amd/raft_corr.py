@@ -1,0 +1,109 @@
+"""RAFT's on-demand correlation lookup on the GPU: a drop-in for RAFT/core/corr.py's AlternateCorrBlock and for the `alt_cuda_corr`
+extension it calls (RAFT/alt_cuda_corr), which has no ROCm build.
+
+Two ways in:
+
+    from mpiflow_amd.raft_corr import AlternateCorrBlock            # corr_fn = AlternateCorrBlock(fmap1, fmap2, radius=r); corr_fn(coords1)
+
+    import sys, mpiflow_amd.raft_corr                               # or: leave RAFT's own corr.py as it is
+    sys.modules["alt_cuda_corr"] = mpiflow_amd.raft_corr            # before `import corr`
+
+The class holds the two feature maps channel-last (fmap1 once, fmap2 as its avg_pool2d pyramid) - nothing quadratic in H * W - and every
+lookup is ONE launch of mpf_corr_lookup for all levels.  It is differentiable with respect to fmap1 and fmap2 (the kernel's gradient,
+mpf_corr_lookup_backward, then torch's own backward of the permutes and of avg_pool2d); coords get NO gradient: the function returns None for
+them, as RAFT detaches coords1 before every lookup (RAFT/core/raft.py:123) and upstream's backward returns zeros there.
+
+What differs from upstream: one launch for all levels instead of one per level plus two permutes per level and lookup; gradients are wired
+(upstream's AlternateCorrBlock calls the extension's forward outside autograd: it is inference-only); coordinates may hold any value - NaN,
++-inf and far-out values give exactly 0 and no gradient; levels smaller than 2 x 2 (H or W < 2^num_levels) are refused, where the
+reference's sampler divides by zero.  There is no CPU path and no eager fallback: MpiFlowHipError.
+"""
+import torch
+import torch.nn.functional as F
+
+from . import ops
+from ._lib import CORR_MAX_LEVELS, MpiFlowHipError
+
+
+class _CorrLookup(torch.autograd.Function):
+    """out = corr_lookup(fmap1_nhwc, levels, coords); gradients for fmap1_nhwc and every level, None for coords and radius."""
+
+    @staticmethod
+    def forward(ctx, coords, radius, fmap1_nhwc, *levels):
+        ctx.radius = radius
+        ctx.save_for_backward(coords, fmap1_nhwc, *levels)
+        return ops.corr_lookup(fmap1_nhwc, levels, coords, radius)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        coords, fmap1_nhwc, *levels = ctx.saved_tensors
+        g1, g2 = ops.corr_lookup_backward(fmap1_nhwc, levels, coords, grad_out.contiguous(), ctx.radius)
+        return (None, None, g1) + tuple(g2)
+
+
+def _check_map(t, name):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise MpiFlowHipError("AlternateCorrBlock: %s must be a tensor on the GPU (got %s); mpiflow_amd has no CPU path"
+                              % (name, t.device if isinstance(t, torch.Tensor) else type(t).__name__))
+    if t.dtype != torch.float32:
+        raise MpiFlowHipError("AlternateCorrBlock: %s must be float32 (got %s)" % (name, t.dtype))
+    if t.dim() != 4 or not t.is_contiguous():
+        raise MpiFlowHipError("AlternateCorrBlock: %s must be a contiguous [B,C,H,W] tensor (got shape %s, contiguous %s)"
+                              % (name, tuple(t.shape), t.is_contiguous()))
+
+
+class AlternateCorrBlock:
+    """RAFT/core/corr.py's AlternateCorrBlock: AlternateCorrBlock(fmap1, fmap2, num_levels=4, radius=4)(coords) -> [B, L*(2r+1)^2, H, W],
+    CorrBlock's result (same channel order: the first window index moves x) without the all-pairs volume.  fmap1, fmap2 [B,C,H,W] float32,
+    contiguous, on the GPU, C a multiple of 32, H and W at least 2^num_levels; coords [B,2,H,W] (x, y), any values.  Usable as `corr_fn` in
+    RAFT/core/raft.py:104-107 unchanged.  No gradient flows to coords (None)."""
+
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
+        _check_map(fmap1, "fmap1")
+        _check_map(fmap2, "fmap2")
+        if fmap1.shape != fmap2.shape or fmap1.device != fmap2.device:
+            raise MpiFlowHipError("AlternateCorrBlock: fmap1 %s on %s and fmap2 %s on %s must agree"
+                                  % (tuple(fmap1.shape), fmap1.device, tuple(fmap2.shape), fmap2.device))
+        B, C, H, W = fmap1.shape
+        if not 1 <= int(num_levels) <= CORR_MAX_LEVELS:
+            raise MpiFlowHipError("AlternateCorrBlock: num_levels must be 1..%d (got %s)" % (CORR_MAX_LEVELS, num_levels))
+        if not 1 <= int(radius) <= 8:
+            raise MpiFlowHipError("AlternateCorrBlock: radius must be 1..8 (got %s)" % (radius,))
+        if C < 32 or C % 32:
+            raise MpiFlowHipError("AlternateCorrBlock: C must be a multiple of 32 (got %d)" % C)
+        if min(H, W) < 2 ** int(num_levels):
+            raise MpiFlowHipError("AlternateCorrBlock: H, W = %d, %d must be at least 2^num_levels = %d (every level at least 2 x 2)"
+                                  % (H, W, 2 ** int(num_levels)))
+        self.num_levels, self.radius = int(num_levels), int(radius)
+        # the layout change happens here, once per pair, not per lookup; autograd carries the levels' gradients back through avg_pool2d
+        self.fmap1_nhwc = fmap1.permute(0, 2, 3, 1).contiguous()
+        self.f2_levels_nhwc = []
+        for i in range(self.num_levels):
+            if i:
+                fmap2 = F.avg_pool2d(fmap2, 2, stride=2)
+            self.f2_levels_nhwc.append(fmap2.permute(0, 2, 3, 1).contiguous())
+
+    def __call__(self, coords):
+        return _CorrLookup.apply(coords, self.radius, self.fmap1_nhwc, *self.f2_levels_nhwc)
+
+
+def _ext_coords(coords, fmap1):
+    if not isinstance(coords, torch.Tensor) or coords.dim() != 5 or coords.shape[-1] != 2 or tuple(coords.shape[2:4]) != tuple(fmap1.shape[1:3]):
+        raise MpiFlowHipError("alt_cuda_corr: coords must be [B,N,H,W,2] for fmap1 [B,H,W,C] (got %s)"
+                              % (tuple(coords.shape) if isinstance(coords, torch.Tensor) else type(coords).__name__,))
+    return [coords[:, n].permute(0, 3, 1, 2).contiguous() for n in range(coords.shape[1])]
+
+
+def forward(fmap1, fmap2, coords, r):
+    """alt_cuda_corr.forward (RAFT/alt_cuda_corr/correlation.cpp:51-54): fmap1 [B,H,W,C], fmap2 [B,H2,W2,C] (one pyramid level, channel-last),
+    coords [B,N,H,W,2] in pixels of fmap2 -> [corr [B,N,(2r+1)^2,H,W]], NOT scaled by 1/sqrt(C)."""
+    return [torch.stack([ops.corr_lookup(fmap1, [fmap2], c, r, scale=1.0) for c in _ext_coords(coords, fmap1)], dim=1)]
+
+
+def backward(fmap1, fmap2, coords, corr_grad, r):
+    """alt_cuda_corr.backward: -> [fmap1_grad [B,H,W,C], fmap2_grad [B,H2,W2,C], coords_grad [B,N,H,W,2] (zeros, as upstream)]."""
+    g1, g2 = None, None
+    for n, c in enumerate(_ext_coords(coords, fmap1)):
+        a, b = ops.corr_lookup_backward(fmap1, [fmap2], c, corr_grad[:, n].contiguous(), r, scale=1.0)
+        g1, g2 = (a, b[0]) if g1 is None else (g1 + a, g2 + b[0])
+    return [g1, g2, torch.zeros_like(coords)]
