@@ -394,6 +394,48 @@ typedef struct MpfCorrArgs {
 int mpf_corr_lookup(const MpfCorrArgs *a, void *stream);
 int mpf_corr_lookup_backward(const MpfCorrArgs *a, void *stream);
 
+/* RAFT's convex upsampling (RAFT.upsample_flow, RAFT/core/raft.py:72-83) and the per-prediction term of its sequence loss (RAFT/train.py:47-72),
+ * fused.  All tensors f32, contiguous:
+ *   flow  [N,2,H,W];  mask  [N,576,H,W], channel k*64 + i*8 + j = tap k = ky*3 + kx, sub-row i, sub-column j
+ *   p[k,i,j]           = softmax over k of mask[n, k*64+i*8+j, h, w]                       (max-subtracted)
+ *   out[n,c,8h+i,8w+j] = sum_k p[k,i,j] * 8 * flow[n, c, h+ky-1, w+kx-1]                   (a neighbour outside the map is 0 and keeps its weight)
+ * mpf_upsample_flow            writes out f32 [N,2,8H,8W].
+ * mpf_upsample_flow_backward   reads out as the cotangent [N,2,8H,8W], recomputes the softmax; WRITES grad_flow [N,2,H,W] and grad_mask [N,576,H,W].
+ * mpf_flow_loss_term           never forms out in memory.  flow_gt f32 [N,2,8H,8W], valid f32 [N,8H,8W];
+ *                                  v = (valid >= 0.5) & (sqrt(gt_u^2 + gt_v^2) < max_flow)   (fp32),   S = sum over all entries of v * |out - flow_gt|
+ *                              writes term[0] = S / (N*2*8H*8W) (f32, device).  With metrics != NULL it also writes five f64 accumulators of THIS
+ *                              prediction to metrics[0..4]: sum of epe over v, the counts of epe < 1, < 3, < 5 over v, and the count of v
+ *                              (epe = sqrt(du^2 + dv^2) in fp32).
+ * mpf_flow_loss_term_backward  g: ONE f32 on the device, the gradient that reaches term (read by the kernel: no host synchronisation).  WRITES grad_flow
+ *                              and grad_mask for the cotangent g / (N*2*8H*8W) * v * sign(out - flow_gt), sign(0) = 0.
+ * workspace: mpf_upsample_workspace(N, H, W, backward) bytes of device memory, 8-byte aligned, contents irrelevant before and after the call
+ * (backward = 0: the loss term's per-block partials; backward = 1: the two backward calls' tap sums [N,2,9,H,W]); mpf_upsample_flow needs none.
+ * No floating-point atomics: the sums are per-block partials folded in a fixed order (in fp64), grad_flow is gathered from the tap sums, so every
+ * output is bit-identical from run to run.  The mask is read once per call and nothing of its size is written by the forward calls.
+ * Any N, H, W >= 1 with N*576*H*W < 2^31; out, flow_gt and valid 16-byte aligned.  Tensor VALUES are unrestricted: NaN and inf propagate as they
+ * do in torch and no value changes an address.  Validated before anything is launched (MPF_ERR_BAD_ARGUMENT). */
+typedef struct MpfUpsampleArgs {
+    const float *flow;
+    const float *mask;
+    float *out;                  /* upsample forward: written;  upsample backward: the cotangent, read;  loss calls: unused */
+    const float *flow_gt;        /* loss calls */
+    const float *valid;          /* loss calls */
+    const float *g;              /* loss backward: device scalar */
+    float *term;                 /* loss forward: device scalar, written */
+    double *metrics;             /* loss forward: NULL or 5 doubles on the device, written */
+    float *grad_flow;            /* backward calls */
+    float *grad_mask;            /* backward calls */
+    void *workspace;
+    size_t workspace_bytes;
+    int N, H, W;
+    float max_flow;              /* RAFT: 400 */
+} MpfUpsampleArgs;
+size_t mpf_upsample_workspace(int N, int H, int W, int backward);   /* 0 for a shape the calls refuse */
+int mpf_upsample_flow(const MpfUpsampleArgs *a, void *stream);
+int mpf_upsample_flow_backward(const MpfUpsampleArgs *a, void *stream);
+int mpf_flow_loss_term(const MpfUpsampleArgs *a, void *stream);
+int mpf_flow_loss_term_backward(const MpfUpsampleArgs *a, void *stream);
+
 /* [3,H,W] float RGB -> [H,W,3] u8 BGR, clip(rint(x*255))  (utils/utils.py:174-177) */
 int mpf_to_u8_bgr(const float *d_img, int H, int W, uint8_t *d_out, void *stream);
 

@@ -108,6 +108,13 @@ class MpfCorrArgs(ctypes.Structure):
                 ("radius", c_i), ("levels", c_i), ("scale", c_f), ("plain", c_i)]
 
 
+class MpfUpsampleArgs(ctypes.Structure):
+    """struct MpfUpsampleArgs of include/mpiflow_hip.h: RAFT's convex upsampling and its loss term, forward and gradient (device pointers)."""
+    _fields_ = [("flow", c_p), ("mask", c_p), ("out", c_p), ("flow_gt", c_p), ("valid", c_p), ("g", c_p), ("term", c_p), ("metrics", c_p),
+                ("grad_flow", c_p), ("grad_mask", c_p), ("workspace", c_p), ("workspace_bytes", c_sz),
+                ("N", c_i), ("H", c_i), ("W", c_i), ("max_flow", c_f)]
+
+
 MAX_VIEWS = 16          # MPF_MAX_VIEWS
 
 # name -> (restype, argtypes); must list every symbol include/mpiflow_hip.h declares (tests/test_capi.py checks)
@@ -146,6 +153,11 @@ SIGNATURES = {
     "mpf_photometric_pairs": (c_i, [ctypes.POINTER(MpfPhotoSample), c_i, c_i, c_i, c_p, c_sz, c_p]),
     "mpf_corr_lookup": (c_i, [ctypes.POINTER(MpfCorrArgs), c_p]),
     "mpf_corr_lookup_backward": (c_i, [ctypes.POINTER(MpfCorrArgs), c_p]),
+    "mpf_upsample_workspace": (c_sz, [c_i, c_i, c_i, c_i]),
+    "mpf_upsample_flow": (c_i, [ctypes.POINTER(MpfUpsampleArgs), c_p]),
+    "mpf_upsample_flow_backward": (c_i, [ctypes.POINTER(MpfUpsampleArgs), c_p]),
+    "mpf_flow_loss_term": (c_i, [ctypes.POINTER(MpfUpsampleArgs), c_p]),
+    "mpf_flow_loss_term_backward": (c_i, [ctypes.POINTER(MpfUpsampleArgs), c_p]),
     "mpf_src_xyz": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
     "mpf_transform_xyz": (c_i, [c_p, c_p, c_i, c_i64, c_p, c_p]),
     "mpf_homography_sample": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),

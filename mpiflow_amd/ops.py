@@ -714,6 +714,118 @@ def corr_lookup_backward(fmap1_nhwc, f2_levels_nhwc, coords, grad_out, radius, s
     return g1, g2
 
 
+def _up_tensor(t, name, shape, who):
+    """RAFT's upsampling takes its tensors as they are: no silent copy, cast or move.  `shape`: None entries are free."""
+    if not isinstance(t, torch.Tensor):
+        raise _lib.MpiFlowHipError("%s: %s must be a torch.Tensor (got %s)" % (who, name, type(t).__name__))
+    if t.dtype != _f32:
+        hint = "; call .float() on it (a half-precision kernel does not exist)" if t.dtype in (torch.float16, torch.bfloat16) else ""
+        raise _lib.MpiFlowHipError("%s: %s must be float32 (got %s)%s" % (who, name, t.dtype, hint))
+    if t.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, t.shape)):
+        raise _lib.MpiFlowHipError("%s: %s must be %s (got shape %s)" % (who, name, list(shape), tuple(t.shape)))
+    if not t.is_contiguous():
+        raise _lib.MpiFlowHipError("%s: %s must be contiguous" % (who, name))
+    return t
+
+
+def _up_on_gpu(who, **tensors):
+    """after every tensor's own checks, so that a wrong dtype or shape is named as such on any device"""
+    first = None
+    for name, t in tensors.items():
+        if not t.is_cuda:
+            raise _lib.MpiFlowHipError("%s: %s must live on the GPU (got %s); mpiflow_amd has no CPU path" % (who, name, t.device))
+        first = t.device if first is None else first
+        if t.device != first:
+            raise _lib.MpiFlowHipError("%s: %s on %s must share flow's device %s" % (who, name, t.device, first))
+
+
+def _up_args(flow, mask, who, **more):
+    f = _up_tensor(flow, "flow", (None, 2, None, None), who)
+    N, _, H, W = f.shape
+    m = _up_tensor(mask, "mask", (N, 576, H, W), who)
+    _up_on_gpu(who, flow=f, mask=m, **more)
+    a = _lib.MpfUpsampleArgs()
+    a.flow, a.mask, a.N, a.H, a.W = f.data_ptr(), m.data_ptr(), N, H, W
+    return a
+
+
+def _up_loss_args(flow, mask, flow_gt, valid, max_flow, who, **more):
+    N, H, W = (tuple(flow.shape[i] for i in (0, 2, 3)) if isinstance(flow, torch.Tensor) and flow.dim() == 4 else (None, None, None))
+    _up_tensor(flow, "flow", (None, 2, None, None), who)
+    _up_tensor(mask, "mask", (N, 576, H, W), who)
+    gt = _up_tensor(flow_gt, "flow_gt", (N, 2, 8 * H, 8 * W), who)
+    va = _up_tensor(valid, "valid", (N, 8 * H, 8 * W), who)
+    a = _up_args(flow, mask, who, flow_gt=gt, valid=va, **more)
+    a.flow_gt, a.valid, a.max_flow = gt.data_ptr(), va.data_ptr(), float(max_flow)
+    return a
+
+
+def _up_workspace(lib, a, backward, dev):
+    ws = torch.empty(int(lib.mpf_upsample_workspace(a.N, a.H, a.W, backward)) // 8, dtype=torch.float64, device=dev)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 8
+    return ws
+
+
+@_on_device
+def upsample_flow(flow, mask):
+    """mpf_upsample_flow: RAFT's convex upsampling.  flow [N,2,H,W], mask [N,576,H,W] -> [N,2,8H,8W]: per fine pixel the softmax over the mask's
+    9 taps blends the 3 x 3 neighbourhood of 8 * flow.  float32, contiguous, on the GPU, or MpiFlowHipError.  Asynchronous on the current stream."""
+    lib = _lib.load()
+    a = _up_args(flow, mask, "upsample_flow")
+    out = torch.empty((a.N, 2, 8 * a.H, 8 * a.W), dtype=_f32, device=flow.device)
+    a.out = out.data_ptr()
+    _lib.check(lib.mpf_upsample_flow(ctypes.byref(a), _stream()), "mpf_upsample_flow")
+    return out
+
+
+@_on_device
+def upsample_flow_backward(flow, mask, grad_out):
+    """mpf_upsample_flow_backward: the cotangent grad_out [N,2,8H,8W] of upsample_flow -> (grad_flow, grad_mask); the softmax is recomputed, no
+    atomics: bit-identical from run to run.  Asynchronous on the current stream."""
+    lib = _lib.load()
+    g = _up_tensor(grad_out, "grad_out", (None, 2, None, None), "upsample_flow_backward")
+    a = _up_args(flow, mask, "upsample_flow_backward", grad_out=g)
+    if tuple(g.shape) != (a.N, 2, 8 * a.H, 8 * a.W):
+        raise _lib.MpiFlowHipError("upsample_flow_backward: grad_out must be %s (got shape %s)" % ([a.N, 2, 8 * a.H, 8 * a.W], tuple(g.shape)))
+    gf, gm = torch.empty_like(flow), torch.empty_like(mask)
+    ws = _up_workspace(lib, a, 1, flow.device)
+    a.out, a.grad_flow, a.grad_mask = g.data_ptr(), gf.data_ptr(), gm.data_ptr()
+    _lib.check(lib.mpf_upsample_flow_backward(ctypes.byref(a), _stream()), "mpf_upsample_flow_backward")
+    del ws
+    return gf, gm
+
+
+@_on_device
+def flow_loss_term(flow, mask, flow_gt, valid, max_flow=400, metrics=False):
+    """mpf_flow_loss_term: (v * |upsample_flow(flow, mask) - flow_gt|).mean() as a 0-d device tensor without forming the prediction;
+    v = (valid >= 0.5) & (|flow_gt| < max_flow).  flow_gt [N,2,8H,8W], valid [N,8H,8W].  With metrics=True also a float64 device tensor of five
+    accumulators of this prediction: sum of epe over v, counts of epe < 1, < 3, < 5, count of v.  -> (term, accumulators or None).  Asynchronous."""
+    lib = _lib.load()
+    a = _up_loss_args(flow, mask, flow_gt, valid, max_flow, "flow_loss_term")
+    term = torch.empty((), dtype=_f32, device=flow.device)
+    acc = torch.empty(5, dtype=torch.float64, device=flow.device) if metrics else None
+    ws = _up_workspace(lib, a, 0, flow.device)
+    a.term, a.metrics = term.data_ptr(), (acc.data_ptr() if metrics else None)
+    _lib.check(lib.mpf_flow_loss_term(ctypes.byref(a), _stream()), "mpf_flow_loss_term")
+    del ws
+    return term, acc
+
+
+@_on_device
+def flow_loss_term_backward(flow, mask, flow_gt, valid, g, max_flow=400):
+    """mpf_flow_loss_term_backward: g, a float32 scalar ON THE DEVICE (the gradient reaching the term; the kernel reads it, the host does not)
+    -> (grad_flow, grad_mask) of flow_loss_term.  Bit-identical from run to run.  Asynchronous on the current stream."""
+    lib = _lib.load()
+    g = _up_tensor(g, "g", (), "flow_loss_term_backward")
+    a = _up_loss_args(flow, mask, flow_gt, valid, max_flow, "flow_loss_term_backward", g=g)
+    gf, gm = torch.empty_like(flow), torch.empty_like(mask)
+    ws = _up_workspace(lib, a, 1, flow.device)
+    a.g, a.grad_flow, a.grad_mask = g.data_ptr(), gf.data_ptr(), gm.data_ptr()
+    _lib.check(lib.mpf_flow_loss_term_backward(ctypes.byref(a), _stream()), "mpf_flow_loss_term_backward")
+    del ws
+    return gf, gm
+
+
 @_on_device
 def to_u8_bgr(img_3HW):
     lib = _lib.load()
