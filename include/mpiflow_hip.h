@@ -193,6 +193,51 @@ int mpf_warp_views_blend_next_merge_prev(const float *d_rgba, const MpfWarpView 
                                          const float *d_obj_mask_next, float *d_quads_next, float *d_quads_complement_next,
                                          const float *d_cum_mask_next, int S, int H, int W, const MpfMergeArgs *merge_prev, void *stream);
 
+/* ---- mask support maps: Stage B tiles the merge cannot read are not rendered ----------------------------------------------------
+ * The merge (utils/utils.py:270-283) takes a view's rgb only where that view's composited object mask reaches the threshold, and that mask
+ * is sum_s weights_s * warped_mask_s (utils/mpi/mpi_rendering.py:95-96): exactly 0 wherever every bilinear tap of the mask is 0 on every
+ * plane.  The reference renders view 0 with obj_mask - ONE instance of the image (gen_3dphoto_dynamic_v2.py:101-105) - and view 1 with
+ * 1 - obj_mask (utils/utils.py:210-236), so most target tiles of view 0 see no mask at all.
+ *   A SUPPORT MAP is a uint32 [ceil(H / MPF_SUPPORT_CELL_H), ceil(W / MPF_SUPPORT_CELL_W)] over the source frame.  Stage A+C, where it writes a
+ * mask-quad buffer, stores `tag` into every cell that holds a quad with a non-zero component (-0.0 counts as zero); other cells are left
+ * alone.  Stage B, given (d_cells, tag) for a view, treats the cells EQUAL to tag as live: give every pair a tag of its own (a counter;
+ * start from a zeroed map and tag 1) and a map never needs clearing.  A Stage B tile (32 x 8 target pixels) is DEAD when on every plane the
+ * homography's denominator is finite and positive at the tile's four corner pixels and the corners' bounding box, widened by one texel
+ * and clamped to the frame, touches no live cell; everything else is rendered as before.
+ *   OUTPUT CONTRACT with a support map: a view's d_rgb / d_objmask / d_rgb_u8_bgr hold the full render's values except on dead tiles, where
+ * d_objmask is 0 (the full render's value there for finite inputs) and d_rgb / d_rgb_u8_bgr are 0 (the full render's value is never selected
+ * by mpf_merge with thresh > 0).  flow_mix / frame_mix / fill_mask of the merge are bit-identical to the full render's.
+ *   A view renders every tile (the launcher decides, per view) when d_cells is NULL, when thresh <= 0 (then `0 >= thresh` selects the view),
+ * or when it asks for d_depth or d_tgt_mask, which do not depend on the mask. */
+#define MPF_SUPPORT_CELL_W 32
+#define MPF_SUPPORT_CELL_H 8
+#define MPF_SUPPORT_CELLS(H, W) ((((H) + MPF_SUPPORT_CELL_H - 1) / MPF_SUPPORT_CELL_H) * (((W) + MPF_SUPPORT_CELL_W - 1) / MPF_SUPPORT_CELL_W))
+typedef struct MpfViewSupport {
+    const uint32_t *d_cells;     /* the support map of the view's d_mask_quads, or NULL */
+    uint32_t tag;                /* the value live cells carry */
+    float thresh;                /* the threshold the views will be merged with */
+} MpfViewSupport;
+
+/* mpf_src_blend_flow that also writes the support maps of d_quads / d_quads_complement (each optional, needs its quads). */
+int mpf_src_blend_flow_support(const float *d_mpi, const float *d_img, const float *d_params, int P, int S, int H, int W,
+                               float flow_clip, float *d_out_rgba, float *d_out_rgb_planar, float *d_out_tacc,
+                               float *d_flows, uint8_t *d_src_u8_bgr, const float *d_obj_mask, float *d_quads,
+                               float *d_quads_complement, const float *d_cum_mask, uint32_t *d_support, uint32_t *d_support_complement,
+                               uint32_t tag, void *stream);
+/* mpf_warp_composite_views with one MpfViewSupport per view (`supports`: host array of n_views, or NULL = mpf_warp_composite_views). */
+int mpf_warp_composite_views_support(const float *d_rgba, int interleaved, const MpfWarpView *views, const MpfViewSupport *supports, int n_views,
+                                     int S, int H, int W, void *stream);
+/* mpf_warp_views_blend_next_merge_prev: the views test `supports`, the Stage A+C role writes the next pair's maps with tag_next.  A map
+ * this launch writes must not be one it tests (the two halves are unordered); outputs otherwise equal the two stand-alone calls above. */
+int mpf_warp_views_blend_next_merge_prev_support(const float *d_rgba, const MpfWarpView *views, const MpfViewSupport *supports, int n_views,
+                                                 const float *d_mpi_next, const float *d_img_next, const float *d_params_next, int P,
+                                                 float flow_clip, float *d_out_rgba_next, float *d_flows_next, uint8_t *d_src_u8_bgr_next,
+                                                 const float *d_obj_mask_next, float *d_quads_next, float *d_quads_complement_next,
+                                                 const float *d_cum_mask_next, uint32_t *d_support_next, uint32_t *d_support_complement_next,
+                                                 uint32_t tag_next, int S, int H, int W, const MpfMergeArgs *merge_prev, void *stream);
+/* The device's decision itself: d_dead [n_views, ceil(H/8) * ceil(W/32)] uint8, 1 where the launches above skip the tile (row-major tiles). */
+int mpf_support_dead_tiles(const MpfWarpView *views, const MpfViewSupport *supports, int n_views, int S, int H, int W, uint8_t *d_dead, void *stream);
+
 /* Stage D.  Replaces utils/utils.py:237-283 (uint8 BGR conversion, threshold, layer select, fill mask).
  * frames [3,H,W] RGB float, masks [H,W], flows [2,H,W], obj_mask [H,W] ->
  * d_flow_mix [H,W,2] f32, d_frame_mix [H,W,3] u8 BGR, d_fill_mask [H,W] u8 (1 = hole to inpaint). */

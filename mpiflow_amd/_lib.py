@@ -62,6 +62,11 @@ class MpfWarpView(ctypes.Structure):
                 ("d_tgt_mask", c_p), ("d_rgb_u8_bgr", c_p)]
 
 
+class MpfViewSupport(ctypes.Structure):
+    """struct MpfViewSupport of include/mpiflow_hip.h: the mask support map one view of a Stage B launch tests (device pointer, tag, merge threshold)."""
+    _fields_ = [("d_cells", c_p), ("tag", ctypes.c_uint32), ("thresh", c_f)]
+
+
 class MpfMovingObjectOut(ctypes.Structure):
     """struct MpfMovingObjectOut of include/mpiflow_hip.h: the output buffers of mpf_moving_object_chain (device pointers)."""
     _fields_ = [("d_p1", c_p), ("d_z1", c_p), ("d_safe_x", c_p), ("d_safe_y", c_p), ("d_flow01", c_p), ("d_warped", c_p),
@@ -116,6 +121,7 @@ class MpfUpsampleArgs(ctypes.Structure):
 
 
 MAX_VIEWS = 16          # MPF_MAX_VIEWS
+SUPPORT_CELL_W, SUPPORT_CELL_H = 32, 8      # MPF_SUPPORT_CELL_W / _H
 
 # name -> (restype, argtypes); must list every symbol include/mpiflow_hip.h declares (tests/test_capi.py checks)
 SIGNATURES = {
@@ -134,6 +140,11 @@ SIGNATURES = {
     "mpf_warp_views_and_blend_next": (c_i, [c_p, ctypes.POINTER(MpfWarpView), c_i, c_p, c_p, c_p, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
     "mpf_warp_views_blend_next_merge_prev": (c_i, [c_p, ctypes.POINTER(MpfWarpView), c_i, c_p, c_p, c_p, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i,
                                                   ctypes.POINTER(MpfMergeArgs), c_p]),
+    "mpf_src_blend_flow_support": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_uint32, c_p]),
+    "mpf_warp_composite_views_support": (c_i, [c_p, c_i, ctypes.POINTER(MpfWarpView), ctypes.POINTER(MpfViewSupport), c_i, c_i, c_i, c_i, c_p]),
+    "mpf_warp_views_blend_next_merge_prev_support": (c_i, [c_p, ctypes.POINTER(MpfWarpView), ctypes.POINTER(MpfViewSupport), c_i, c_p, c_p, c_p, c_i, c_f, c_p, c_p, c_p,
+                                                          c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_uint32, c_i, c_i, c_i, ctypes.POINTER(MpfMergeArgs), c_p]),
+    "mpf_support_dead_tiles": (c_i, [ctypes.POINTER(MpfWarpView), ctypes.POINTER(MpfViewSupport), c_i, c_i, c_i, c_i, c_p, c_p]),
     "mpf_merge": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_i, c_i, c_p, c_p, c_p, c_p]),
     "mpf_merge_ex": (c_i, [ctypes.POINTER(MpfMergeArgs), c_i, c_i, c_p]),
     "mpf_merge_depth_ordered": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_i, c_i, c_p, c_p, c_p]),

@@ -642,6 +642,83 @@ k_warp_composite_v2(const float *__restrict__ rgba, const float *__restrict__ qu
                                              mpf_strip_order(mpf_xcd_remap(blockIdx.x, gridDim.x), (W + TW - 1) / TW, (H + TH - 1) / TH));
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Mask support maps: Stage B tiles whose object-mask taps are all zero are not rendered.
+//
+// A pair's merge (mpf_merge_pixel, utils/utils.py:270-283) reads a view's rgb only where that view's composited mask reaches the threshold,
+// and the composited mask is sum_s w_s * (bilinear tap of the mask quads) (utils/mpi/mpi_rendering.py:95-96): where every tap of every
+// plane is exactly zero it is exactly 0, whatever rgb and sigma are.  Stage A+C records, per MPF_SUPPORT_CELL_W x MPF_SUPPORT_CELL_H cell of
+// the SOURCE frame, whether any mask quad of the cell has a non-zero component (a quad already holds its east / south neighbours), by
+// storing the pair's generation tag into the cell's uint32: every writer of a cell stores the same value, the reader compares for
+// equality, so what an earlier pair left in the map never counts and nothing is ever cleared.  A Stage B workgroup maps its tile's four
+// corner pixel centres through every plane's homography (lane = plane) and is DEAD if, on every plane, the four denominators are finite
+// and positive - the projective map then keeps the tile inside the hull of its corners - and the corners' bounding box, widened by one
+// texel for rounding and clamped to the frame as border-mode sampling clamps, touches no cell carrying the tag.  Anything the test cannot
+// bound counts as alive.  A dead tile gets objmask = 0 (the full render's value) and rgb = 0 (never selected by the merge).
+// Every wave of the workgroup runs the whole test on its own (same inputs, same result): no LDS, no barrier, and its registers are dead
+// before the plane loop starts.
+// ---------------------------------------------------------------------------------------------------------------
+struct MpfSupportSet {
+    const unsigned *cells[MPF_MAX_VIEWS];   // nullptr: the view renders every tile
+    unsigned tag[MPF_MAX_VIEWS];
+};
+
+#define MPF_SUPPORT_MAX_CELLS 32            // a plane whose box covers more cells than this is not searched: the tile counts as alive
+
+template <int TW, int TH>
+MPF_DEV bool mpf_tile_dead(const MpfConstParams params, const unsigned *__restrict__ cells, const unsigned tag, const int S, const int H, const int W,
+                           const unsigned tile)
+{
+    const unsigned tiles_x = (W + TW - 1) / TW;
+    const int tx0 = (int)(tile % tiles_x) * TW, ty0 = (int)(tile / tiles_x) * TH;
+    // lanes past the image edge shadow the last pixel (mpf_wc2_body), so the corners are clamped the same way
+    const float xs[2] = { (float)tx0, (float)min(tx0 + TW - 1, W - 1) }, ys[2] = { (float)ty0, (float)min(ty0 + TH - 1, H - 1) };
+    const float maxx = (float)(W - 1), maxy = (float)(H - 1);
+    const int cells_x = (W + MPF_SUPPORT_CELL_W - 1) / MPF_SUPPORT_CELL_W;
+    bool alive = false;
+    for (int s = (int)(threadIdx.x & 63u); s < S; s += 64) {
+        const MpfConstParams rec = params + MPF_PARAMS_HEADER + MPF_PLANE_RECORD * s;
+        float ulo = INFINITY, uhi = -INFINITY, vlo = INFINITY, vhi = -INFINITY;
+        bool ok = true;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float px = xs[k & 1], py = ys[k >> 1];
+            const float qx = mpf_row3_xy1(rec[0], rec[1], rec[2], px, py);
+            const float qy = mpf_row3_xy1(rec[3], rec[4], rec[5], px, py);
+            const float qz = mpf_row3_xy1(rec[6], rec[7], rec[8], px, py);
+            ok = ok && (qz > 0.0f) && (qz < INFINITY);
+            const float u = qx / qz, v = qy / qz;
+            ulo = fminf(ulo, u); uhi = fmaxf(uhi, u);
+            vlo = fminf(vlo, v); vhi = fmaxf(vhi, v);
+        }
+        ok = ok && (ulo > -1e9f) && (uhi < 1e9f) && (vlo > -1e9f) && (vhi < 1e9f);      // false for NaN as well
+        if (!ok) { alive = true; continue; }
+        // north-west texel of a pixel's taps: floor(clamp(u, 0, W - 1)) (mpf_geom_core); one texel of margin covers its roundings
+        const int cx0 = (int)fminf(fmaxf(ulo - 1.0f, 0.0f), maxx) / MPF_SUPPORT_CELL_W, cx1 = (int)fminf(fmaxf(uhi + 1.0f, 0.0f), maxx) / MPF_SUPPORT_CELL_W;
+        const int cy0 = (int)fminf(fmaxf(vlo - 1.0f, 0.0f), maxy) / MPF_SUPPORT_CELL_H, cy1 = (int)fminf(fmaxf(vhi + 1.0f, 0.0f), maxy) / MPF_SUPPORT_CELL_H;
+        if ((cx1 - cx0 + 1) * (cy1 - cy0 + 1) > MPF_SUPPORT_MAX_CELLS) { alive = true; continue; }
+        for (int cy = cy0; cy <= cy1; ++cy)
+            for (int cx = cx0; cx <= cx1; ++cx) alive = alive || (cells[cy * cells_x + cx] == tag);
+    }
+    return __ballot(alive) == 0;            // wave-uniform, and the same in every wave of the workgroup
+}
+
+template <int TW, int TH>
+MPF_DEV void mpf_dead_tile_store(const int H, const int W, const unsigned tile, float *__restrict__ rgb_out, float *__restrict__ om_out,
+                                 uint8_t *__restrict__ u8_out)
+{
+    const int64_t N = (int64_t)H * W;
+    const unsigned tiles_x = (W + TW - 1) / TW;
+    const int x = (tile % tiles_x) * TW + (threadIdx.x % TW);
+    const int y = (tile / tiles_x) * TH + (threadIdx.x / TW);
+    if (x < W && y < H) {
+        const int64_t n = (int64_t)y * W + x;
+        rgb_out[n] = 0.0f; rgb_out[N + n] = 0.0f; rgb_out[2 * N + n] = 0.0f;
+        if (u8_out) { u8_out[3 * n] = 0; u8_out[3 * n + 1] = 0; u8_out[3 * n + 2] = 0; }
+        om_out[n] = 0.0f;
+    }
+}
+
 // Several views of ONE stack in one launch (the reference renders two poses of every stack, utils/utils.py:210-236, and
 // `repeat` such pairs per image, gen_3dphoto_dynamic_v2.py:99-118).  Logical block l = tile * V + view: the V workgroups of a
 // tile are dispatched back to back on the same XCD, walk the planes at the same pace and so find each other's texels in
@@ -651,7 +728,8 @@ struct MpfViewSet { MpfWarpView v[MPF_MAX_VIEWS]; };
 
 template <bool HAS_MASK, int NL, int TW, int TH, int WPS, bool TP>
 __global__ void __launch_bounds__(TW *TH, WPS)
-k_warp_composite_views(const float *__restrict__ rgba, const MpfViewSet vs, const unsigned V, int S, int H, int W, const unsigned view_shift)
+k_warp_composite_views(const float *__restrict__ rgba, const MpfViewSet vs, const unsigned V, int S, int H, int W, const unsigned view_shift,
+                       const MpfSupportSet ss)
 {
     const unsigned l = mpf_xcd_remap(blockIdx.x, gridDim.x);
     const unsigned view = l % V;
@@ -661,6 +739,10 @@ k_warp_composite_views(const float *__restrict__ rgba, const MpfViewSet vs, cons
     const unsigned seq = (view & 1u) ? (l / V + view_shift) % ntiles : l / V;
     const unsigned tile = mpf_strip_order(seq, tiles_x, tiles_y);
     const MpfWarpView &w = vs.v[view];
+    if (HAS_MASK && ss.cells[view] && mpf_tile_dead<TW, TH>((MpfConstParams)w.d_params, ss.cells[view], ss.tag[view], S, H, W, tile)) {
+        mpf_dead_tile_store<TW, TH>(H, W, tile, w.d_rgb, w.d_objmask, w.d_rgb_u8_bgr);
+        return;
+    }
     mpf_wc2_select<HAS_MASK, NL, TW, TH, TP>(rgba, w.d_mask_quads, w.d_params, S, H, W, w.d_rgb, w.d_depth, w.d_objmask, w.d_tgt_mask,
                                              w.d_rgb_u8_bgr, tile);
 }
@@ -1287,20 +1369,34 @@ extern "C" int mpf_warp_composite(const float *d_rgba, int interleaved, const fl
 MPF_KNOB g_view_shift = 8;
 
 template <bool HAS_MASK>
-static int launch_views(bool tp, const float *rgba, const MpfViewSet &vs, int V, int S, int H, int W, hipStream_t st)
+static int launch_views(bool tp, const float *rgba, const MpfViewSet &vs, int V, int S, int H, int W, hipStream_t st, const MpfSupportSet &ss)
 {
     constexpr int TW = 32, TH = 8, WPS = 5;
     const unsigned tiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
     dim3 grid(tiles * (unsigned)V), block(TW * TH);
-#define MPF_WCV(NLv, TPv) hipLaunchKernelGGL((k_warp_composite_views<HAS_MASK, NLv, TW, TH, WPS, TPv>), grid, block, 0, st, rgba, vs, (unsigned)V, S, H, W, (unsigned)g_view_shift % tiles)
+#define MPF_WCV(NLv, TPv) hipLaunchKernelGGL((k_warp_composite_views<HAS_MASK, NLv, TW, TH, WPS, TPv>), grid, block, 0, st, rgba, vs, (unsigned)V, S, H, W, (unsigned)g_view_shift % tiles, ss)
     if (S < 256) { if (tp) MPF_WCV(2, true); else MPF_WCV(2, false); }
     else         { if (tp) MPF_WCV(3, true); else MPF_WCV(3, false); }
 #undef MPF_WCV
     return mpf_launch_status("k_warp_composite_views");
 }
 
-extern "C" int mpf_warp_composite_views(const float *d_rgba, int interleaved, const MpfWarpView *views, int n_views, int S, int H,
-                                        int W, void *stream)
+// The per-view support maps a launch may test (see mpf_tile_dead).  A view renders every tile when it was given no map, when the merge could select it
+// without its mask reaching the threshold (thresh <= 0: `0 >= thresh` holds), or when it asks for depth / tgt_mask, which do not depend on the mask.
+static MpfSupportSet mpf_support_set(const MpfWarpView *views, const MpfViewSupport *supports, int n_views, bool has_mask)
+{
+    MpfSupportSet ss;
+    memset(&ss, 0, sizeof(ss));
+    for (int v = 0; supports && has_mask && v < n_views; ++v) {
+        const bool allowed = supports[v].d_cells && supports[v].thresh > 0.0f && !views[v].d_depth && !views[v].d_tgt_mask;
+        ss.cells[v] = allowed ? supports[v].d_cells : nullptr;
+        ss.tag[v] = supports[v].tag;
+    }
+    return ss;
+}
+
+static int warp_composite_views_impl(const float *d_rgba, int interleaved, const MpfWarpView *views, const MpfViewSupport *supports, int n_views, int S, int H,
+                                     int W, void *stream)
 {
     MPF_REQUIRE(d_rgba && views, "mpf_warp_composite_views: null pointer");
     MPF_REQUIRE(n_views >= 1 && n_views <= MPF_MAX_VIEWS, "mpf_warp_composite_views: n_views must be 1..%d (got %d)", MPF_MAX_VIEWS, n_views);
@@ -1319,14 +1415,57 @@ extern "C" int mpf_warp_composite_views(const float *d_rgba, int interleaved, co
         MPF_REQUIRE(mpf_aligned16(w.d_mask_quads), "mpf_warp_composite_views: view %d: mask quads must be 16-byte aligned", v);
         vs.v[v] = w;
     }
+    const MpfSupportSet ss = mpf_support_set(views, supports, n_views, has_mask);
 #ifdef MPF_WITNESS
-    if (g_stage_b_variant == 20 && interleaved == 2 && S <= MPF_LT_MAXS) {
+    if (g_stage_b_variant == 20 && interleaved == 2 && S <= MPF_LT_MAXS) {          // the retired LDS-staged variant renders every tile
         if (has_mask) return launch_lds<true>(d_rgba, vs, n_views, S, H, W, (hipStream_t)stream);
         return launch_lds<false>(d_rgba, vs, n_views, S, H, W, (hipStream_t)stream);
     }
 #endif
-    if (has_mask) return launch_views<true>(interleaved == 2, d_rgba, vs, n_views, S, H, W, (hipStream_t)stream);
-    return launch_views<false>(interleaved == 2, d_rgba, vs, n_views, S, H, W, (hipStream_t)stream);
+    if (has_mask) return launch_views<true>(interleaved == 2, d_rgba, vs, n_views, S, H, W, (hipStream_t)stream, ss);
+    return launch_views<false>(interleaved == 2, d_rgba, vs, n_views, S, H, W, (hipStream_t)stream, ss);
+}
+
+extern "C" int mpf_warp_composite_views(const float *d_rgba, int interleaved, const MpfWarpView *views, int n_views, int S, int H,
+                                        int W, void *stream)
+{
+    return warp_composite_views_impl(d_rgba, interleaved, views, nullptr, n_views, S, H, W, stream);
+}
+
+extern "C" int mpf_warp_composite_views_support(const float *d_rgba, int interleaved, const MpfWarpView *views, const MpfViewSupport *supports, int n_views,
+                                                int S, int H, int W, void *stream)
+{
+    return warp_composite_views_impl(d_rgba, interleaved, views, supports, n_views, S, H, W, stream);
+}
+
+// The decision of mpf_tile_dead itself, one wave per (view, tile): d_dead[view * tiles + tile] = 1 where the launches above would skip the tile.
+__global__ void __launch_bounds__(256)
+k_support_dead_tiles(const MpfViewSet vs, const MpfSupportSet ss, const unsigned V, const int S, const int H, const int W, uint8_t *__restrict__ dead)
+{
+    constexpr int TW = 32, TH = 8;
+    const unsigned tiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
+    const unsigned j = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (j >= V * tiles) return;
+    const unsigned view = j / tiles, tile = j % tiles;
+    const bool d = ss.cells[view] && mpf_tile_dead<TW, TH>((MpfConstParams)vs.v[view].d_params, ss.cells[view], ss.tag[view], S, H, W, tile);
+    if ((threadIdx.x & 63u) == 0) dead[j] = d ? 1 : 0;
+}
+
+extern "C" int mpf_support_dead_tiles(const MpfWarpView *views, const MpfViewSupport *supports, int n_views, int S, int H, int W, uint8_t *d_dead, void *stream)
+{
+    MPF_REQUIRE(views && supports && d_dead, "mpf_support_dead_tiles: null pointer");
+    MPF_REQUIRE(n_views >= 1 && n_views <= MPF_MAX_VIEWS, "mpf_support_dead_tiles: n_views must be 1..%d (got %d)", MPF_MAX_VIEWS, n_views);
+    MPF_REQUIRE(S >= 1 && S < 4096 && H >= 1 && W >= 1 && (int64_t)H * W < ((int64_t)1 << 27), "mpf_support_dead_tiles: bad shape S=%d H=%d W=%d", S, H, W);
+    MpfViewSet vs;
+    memset(&vs, 0, sizeof(vs));
+    for (int v = 0; v < n_views; ++v) {
+        MPF_REQUIRE(views[v].d_params, "mpf_support_dead_tiles: view %d: null params", v);
+        vs.v[v] = views[v];
+    }
+    const MpfSupportSet ss = mpf_support_set(views, supports, n_views, views[0].d_mask_quads != nullptr);
+    const unsigned tiles = ((W + 31) / 32) * ((H + 7) / 8);
+    hipLaunchKernelGGL(k_support_dead_tiles, dim3((tiles * (unsigned)n_views + 3) / 4), dim3(256), 0, (hipStream_t)stream, vs, ss, (unsigned)n_views, S, H, W, d_dead);
+    return mpf_launch_status("k_support_dead_tiles");
 }
 
 // mask quads ---------------------------------------------------------------------------------------------------
@@ -1396,7 +1535,19 @@ struct MpfSbfArgs {
     const float *cum_mask;
     int64_t plane_stride, sigma_off;   // floats: plane s starts at mpi + s * plane_stride, its sigma channel sigma_off further
                                        // ([S,4,H,W]: 4 N and 3 N; a bare sigma tensor [S,H,W] for the flow-only pass: N and 0)
+    unsigned *sup, *sup_c;             // support maps of quads / quads_c (see mpf_tile_dead), nullptr = none; every live cell gets `tag`
+    unsigned tag;
 };
+
+// By-product of the mask quads: the cell of pixel (x, y) is live in a support map if the pixel's quad has a non-zero component (-0.0 is zero,
+// NaN is not).  All writers of a cell store the same tag - plain vector stores, no atomics, nothing to clear.
+MPF_DEV void mpf_support_mark(const MpfSbfArgs &a, const int x, const int y, const int W, const float q0, const float q1, const float q2, const float q3,
+                              const float c0, const float c1, const float c2, const float c3)
+{
+    const unsigned cell = (unsigned)(y / MPF_SUPPORT_CELL_H) * (unsigned)((W + MPF_SUPPORT_CELL_W - 1) / MPF_SUPPORT_CELL_W) + (unsigned)(x / MPF_SUPPORT_CELL_W);
+    if (a.sup && ((q0 != 0.0f) | (q1 != 0.0f) | (q2 != 0.0f) | (q3 != 0.0f))) a.sup[cell] = a.tag;
+    if (a.sup_c && ((c0 != 0.0f) | (c1 != 0.0f) | (c2 != 0.0f) | (c3 != 0.0f))) a.sup_c[cell] = a.tag;
+}
 
 template <int PX, int P, int NL, bool ACT, bool BLEND, bool NT_STORE, int DEPTH>
 MPF_DEV void mpf_sbf_body(const MpfSbfArgs &a, const int S, const int H, const int W, const int64_t t)
@@ -1459,8 +1610,10 @@ MPF_DEV void mpf_sbf_body(const MpfSbfArgs &a, const int S, const int H, const i
             const float b = e ? obj_mask[n[i] + 1] : 0.0f;
             const float c2 = so ? obj_mask[n[i] + W] : 0.0f;
             const float d2 = (e && so) ? obj_mask[n[i] + W + 1] : 0.0f;
+            const float4 qc = make_float4(1.0f - a0, e ? 1.0f - b : 0.0f, so ? 1.0f - c2 : 0.0f, (e && so) ? 1.0f - d2 : 0.0f);
             if (quads) quads[n[i]] = make_float4(a0, b, c2, d2);
-            if (quads_c) quads_c[n[i]] = make_float4(1.0f - a0, e ? 1.0f - b : 0.0f, so ? 1.0f - c2 : 0.0f, (e && so) ? 1.0f - d2 : 0.0f);
+            if (quads_c) quads_c[n[i]] = qc;
+            mpf_support_mark(a, x, y, W, a0, b, c2, d2, qc.x, qc.y, qc.z, qc.w);
         }
     }
 
@@ -1583,16 +1736,19 @@ k_src_blend_flow(const float *__restrict__ mpi, const float *__restrict__ img, c
                  int H, int W, float flow_clip, float *__restrict__ out_rgba, float *__restrict__ out_planar,
                  float *__restrict__ out_tacc, float *__restrict__ flows, int64_t T, uint8_t *__restrict__ src_u8,
                  const float *__restrict__ obj_mask, float4 *__restrict__ quads, float4 *__restrict__ quads_c,
-                 const float *__restrict__ cum_mask, int64_t plane_stride, int64_t sigma_off)
+                 const float *__restrict__ cum_mask, int64_t plane_stride, int64_t sigma_off, unsigned *__restrict__ sup, unsigned *__restrict__ sup_c,
+                 unsigned tag)
 {
-    const MpfSbfArgs a = { mpi, img, params, flow_clip, out_rgba, out_planar, out_tacc, flows, T, src_u8, obj_mask, quads, quads_c, cum_mask, plane_stride, sigma_off };
+    const MpfSbfArgs a = { mpi, img, params, flow_clip, out_rgba, out_planar, out_tacc, flows, T, src_u8, obj_mask, quads, quads_c, cum_mask, plane_stride, sigma_off,
+                           sup, sup_c, tag };
     mpf_sbf_body<PX, P, NL, ACT, BLEND, NT_STORE, 2>(a, S, H, W, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 template <int PX, int P>
 static int launch_sbf(const float *mpi, const float *img, const float *params, int S, int H, int W, float clip,
                       float *rgba, float *planar, float *tacc, float *flows, uint8_t *src_u8, const float *om, float *q0, float *q1,
-                      const float *cum_mask, hipStream_t st, int64_t plane_stride = 0, int64_t sigma_off = 0)
+                      const float *cum_mask, hipStream_t st, int64_t plane_stride = 0, int64_t sigma_off = 0, unsigned *sup = nullptr, unsigned *sup_c = nullptr,
+                      unsigned tag = 0)
 {
     const int64_t N = (int64_t)H * W;
     const int64_t T = (N + PX - 1) / PX;
@@ -1600,7 +1756,7 @@ static int launch_sbf(const float *mpi, const float *img, const float *params, i
     dim3 grid((unsigned)((T + 255) / 256)), block(256);
     const bool blend = rgba || planar || tacc;
 #define MPF_SBF_GO(NLv, ACTv, BLv) hipLaunchKernelGGL((k_src_blend_flow<PX, P, NLv, ACTv, BLv>), grid, block, 0, st, mpi, img, params, S, H, W, clip, rgba, \
-                                              planar, tacc, flows, T, src_u8, om, reinterpret_cast<float4 *>(q0), reinterpret_cast<float4 *>(q1), cum_mask, plane_stride, sigma_off)
+                                              planar, tacc, flows, T, src_u8, om, reinterpret_cast<float4 *>(q0), reinterpret_cast<float4 *>(q1), cum_mask, plane_stride, sigma_off, sup, sup_c, tag)
 #define MPF_SBF_NL(NLv)                                                                              \
     if (cum_mask) { if (blend) MPF_SBF_GO(NLv, true, true); else MPF_SBF_GO(NLv, true, false); }    \
     else          { if (blend) MPF_SBF_GO(NLv, false, true); else MPF_SBF_GO(NLv, false, false); }
@@ -1612,11 +1768,12 @@ static int launch_sbf(const float *mpi, const float *img, const float *params, i
 
 static int g_sbf_px = 0;   // 0 = auto; tuning knob for benches (mpf_tune)
 
-extern "C" int mpf_src_blend_flow(const float *d_mpi, const float *d_img, const float *d_params, int P, int S, int H, int W,
-                                  float flow_clip, float *d_out_rgba, float *d_out_rgb_planar, float *d_out_tacc,
-                                  float *d_flows, uint8_t *d_src_u8_bgr, const float *d_obj_mask, float *d_quads,
-                                  float *d_quads_complement, const float *d_cum_mask, void *stream)
+static int src_blend_flow_impl(const float *d_mpi, const float *d_img, const float *d_params, int P, int S, int H, int W,
+                               float flow_clip, float *d_out_rgba, float *d_out_rgb_planar, float *d_out_tacc,
+                               float *d_flows, uint8_t *d_src_u8_bgr, const float *d_obj_mask, float *d_quads,
+                               float *d_quads_complement, const float *d_cum_mask, unsigned *d_support, unsigned *d_support_complement, unsigned tag, void *stream)
 {
+    MPF_REQUIRE((d_support == nullptr || d_quads) && (d_support_complement == nullptr || d_quads_complement), "mpf_src_blend_flow: a support map needs its quads");
     MPF_REQUIRE(d_mpi && d_img && d_params, "mpf_src_blend_flow: null pointer");
     MPF_REQUIRE((d_quads == nullptr && d_quads_complement == nullptr) || d_obj_mask, "mpf_src_blend_flow: quads need d_obj_mask");
     MPF_REQUIRE(mpf_aligned16(d_quads) && mpf_aligned16(d_quads_complement), "mpf_src_blend_flow: quads must be 16-byte aligned");
@@ -1633,13 +1790,32 @@ extern "C" int mpf_src_blend_flow(const float *d_mpi, const float *d_img, const 
     }
 #define MPF_SBF(PXv)                                                                                                     \
     switch (P) {                                                                                                         \
-    case 0: return launch_sbf<PXv, 0>(d_mpi, d_img, d_params, S, H, W, flow_clip, d_out_rgba, d_out_rgb_planar, d_out_tacc, d_flows, d_src_u8_bgr, (d_quads || d_quads_complement) ? d_obj_mask : nullptr, d_quads, d_quads_complement, d_cum_mask, st); \
-    case 1: return launch_sbf<PXv, 1>(d_mpi, d_img, d_params, S, H, W, flow_clip, d_out_rgba, d_out_rgb_planar, d_out_tacc, d_flows, d_src_u8_bgr, (d_quads || d_quads_complement) ? d_obj_mask : nullptr, d_quads, d_quads_complement, d_cum_mask, st); \
-    default: return launch_sbf<PXv, 2>(d_mpi, d_img, d_params, S, H, W, flow_clip, d_out_rgba, d_out_rgb_planar, d_out_tacc, d_flows, d_src_u8_bgr, (d_quads || d_quads_complement) ? d_obj_mask : nullptr, d_quads, d_quads_complement, d_cum_mask, st); \
+    case 0: return launch_sbf<PXv, 0>(d_mpi, d_img, d_params, S, H, W, flow_clip, d_out_rgba, d_out_rgb_planar, d_out_tacc, d_flows, d_src_u8_bgr, (d_quads || d_quads_complement) ? d_obj_mask : nullptr, d_quads, d_quads_complement, d_cum_mask, st, 0, 0, d_support, d_support_complement, tag); \
+    case 1: return launch_sbf<PXv, 1>(d_mpi, d_img, d_params, S, H, W, flow_clip, d_out_rgba, d_out_rgb_planar, d_out_tacc, d_flows, d_src_u8_bgr, (d_quads || d_quads_complement) ? d_obj_mask : nullptr, d_quads, d_quads_complement, d_cum_mask, st, 0, 0, d_support, d_support_complement, tag); \
+    default: return launch_sbf<PXv, 2>(d_mpi, d_img, d_params, S, H, W, flow_clip, d_out_rgba, d_out_rgb_planar, d_out_tacc, d_flows, d_src_u8_bgr, (d_quads || d_quads_complement) ? d_obj_mask : nullptr, d_quads, d_quads_complement, d_cum_mask, st, 0, 0, d_support, d_support_complement, tag); \
     }
     if (px == 2) { MPF_SBF(2) }
     MPF_SBF(1)
 #undef MPF_SBF
+}
+
+extern "C" int mpf_src_blend_flow(const float *d_mpi, const float *d_img, const float *d_params, int P, int S, int H, int W,
+                                  float flow_clip, float *d_out_rgba, float *d_out_rgb_planar, float *d_out_tacc,
+                                  float *d_flows, uint8_t *d_src_u8_bgr, const float *d_obj_mask, float *d_quads,
+                                  float *d_quads_complement, const float *d_cum_mask, void *stream)
+{
+    return src_blend_flow_impl(d_mpi, d_img, d_params, P, S, H, W, flow_clip, d_out_rgba, d_out_rgb_planar, d_out_tacc, d_flows, d_src_u8_bgr, d_obj_mask, d_quads,
+                               d_quads_complement, d_cum_mask, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int mpf_src_blend_flow_support(const float *d_mpi, const float *d_img, const float *d_params, int P, int S, int H, int W,
+                                          float flow_clip, float *d_out_rgba, float *d_out_rgb_planar, float *d_out_tacc,
+                                          float *d_flows, uint8_t *d_src_u8_bgr, const float *d_obj_mask, float *d_quads,
+                                          float *d_quads_complement, const float *d_cum_mask, uint32_t *d_support, uint32_t *d_support_complement, uint32_t tag,
+                                          void *stream)
+{
+    return src_blend_flow_impl(d_mpi, d_img, d_params, P, S, H, W, flow_clip, d_out_rgba, d_out_rgb_planar, d_out_tacc, d_flows, d_src_u8_bgr, d_obj_mask, d_quads,
+                               d_quads_complement, d_cum_mask, d_support, d_support_complement, tag, stream);
 }
 
 // Stage D for one pixel (utils/utils.py:237-283): thresholds, layer select, uint8 BGR frame, fill mask, merged flow.  Shared by k_merge and
@@ -1735,8 +1911,10 @@ MPF_DEV void mpf_sbf_stream(const MpfSbfArgs &a, const int S, const int H, const
             const float b = e ? a.obj_mask[n[i] + 1] : 0.0f;
             const float c2 = so ? a.obj_mask[n[i] + W] : 0.0f;
             const float d2 = (e && so) ? a.obj_mask[n[i] + W + 1] : 0.0f;
+            const float4 qc = make_float4(1.0f - a0, e ? 1.0f - b : 0.0f, so ? 1.0f - c2 : 0.0f, (e && so) ? 1.0f - d2 : 0.0f);
             if (a.quads) a.quads[n[i]] = make_float4(a0, b, c2, d2);
-            if (a.quads_c) a.quads_c[n[i]] = make_float4(1.0f - a0, e ? 1.0f - b : 0.0f, so ? 1.0f - c2 : 0.0f, (e && so) ? 1.0f - d2 : 0.0f);
+            if (a.quads_c) a.quads_c[n[i]] = qc;
+            mpf_support_mark(a, x, y, W, a0, b, c2, d2, qc.x, qc.y, qc.z, qc.w);
         }
     }
 
@@ -1865,7 +2043,7 @@ template <bool HAS_MASK, int NL, int P, bool ACT, int DEPTH>
 __global__ void __launch_bounds__(256, 5)
 k_pair_overlap(const float *__restrict__ rgba_b, const MpfViewSet vs, const unsigned V, const MpfSbfArgs ac, const int S, const int H, const int W,
                const unsigned nB, const unsigned nA, const unsigned KB, const unsigned KA, const int ablate_, const unsigned view_shift, const unsigned xcd_a_,
-               const MpfMergeArgs mg)
+               const MpfMergeArgs mg, const MpfSupportSet ss)
 {
     constexpr int TW = 32, TH = 8;
     const unsigned xcd = blockIdx.x & 7u, k = blockIdx.x >> 3;          // the k-th workgroup of this XCD
@@ -1904,6 +2082,10 @@ k_pair_overlap(const float *__restrict__ rgba_b, const MpfViewSet vs, const unsi
         const unsigned seq = (view & 1u) ? (l / V + view_shift) % ntiles : l / V;        // see k_warp_composite_views
         const unsigned tile = mpf_strip_order(seq, tiles_x, tiles_y);
         const MpfWarpView &w = vs.v[view];
+        if (HAS_MASK && ss.cells[view] && mpf_tile_dead<TW, TH>((MpfConstParams)w.d_params, ss.cells[view], ss.tag[view], S, H, W, tile)) {
+            mpf_dead_tile_store<TW, TH>(H, W, tile, w.d_rgb, w.d_objmask, w.d_rgb_u8_bgr);
+            return;
+        }
         mpf_wc2_select<HAS_MASK, NL, TW, TH, true>(rgba_b, w.d_mask_quads, w.d_params, S, H, W, w.d_rgb, w.d_depth, w.d_objmask, w.d_tgt_mask,
                                                    w.d_rgb_u8_bgr, tile);
     }
@@ -1914,7 +2096,8 @@ MPF_KNOB g_ovl_ablate = 0;      // mpf_tune("ovl_ablate", 0 | 1 | 2): bench-only
 MPF_KNOB g_ovl_xcd_a = 0;       // mpf_tune("ovl_xcd_a", 0..7): 0 = both roles interleaved on every XCD (Bresenham), n = the first n XCDs run Stage A+C only
 
 template <bool HAS_MASK, int NL, int P, bool ACT>
-static int launch_overlap(const float *rgba_b, const MpfViewSet &vs, unsigned V, const MpfSbfArgs &ac, int S, int H, int W, hipStream_t st, const MpfMergeArgs &mg)
+static int launch_overlap(const float *rgba_b, const MpfViewSet &vs, unsigned V, const MpfSbfArgs &ac, int S, int H, int W, hipStream_t st, const MpfMergeArgs &mg,
+                          const MpfSupportSet &ss)
 {
     const unsigned tiles = ((W + 31) / 32) * ((H + 7) / 8);
     const unsigned nB = tiles * V;
@@ -1929,11 +2112,11 @@ static int launch_overlap(const float *rgba_b, const MpfViewSet &vs, unsigned V,
     dim3 grid(8u * per_xcd), block(256);
 #ifdef MPF_WITNESS
     if (g_ovl_depth == 8) {
-        hipLaunchKernelGGL((k_pair_overlap<HAS_MASK, NL, P, ACT, 8>), grid, block, 0, st, rgba_b, vs, V, ac, S, H, W, nB, nA, KB, KA, g_ovl_ablate, (unsigned)g_view_shift % tiles, xa, mg);
+        hipLaunchKernelGGL((k_pair_overlap<HAS_MASK, NL, P, ACT, 8>), grid, block, 0, st, rgba_b, vs, V, ac, S, H, W, nB, nA, KB, KA, g_ovl_ablate, (unsigned)g_view_shift % tiles, xa, mg, ss);
         return mpf_launch_status("k_pair_overlap");
     }
 #endif
-    hipLaunchKernelGGL((k_pair_overlap<HAS_MASK, NL, P, ACT, 4>), grid, block, 0, st, rgba_b, vs, V, ac, S, H, W, nB, nA, KB, KA, g_ovl_ablate, (unsigned)g_view_shift % tiles, xa, mg);
+    hipLaunchKernelGGL((k_pair_overlap<HAS_MASK, NL, P, ACT, 4>), grid, block, 0, st, rgba_b, vs, V, ac, S, H, W, nB, nA, KB, KA, g_ovl_ablate, (unsigned)g_view_shift % tiles, xa, mg, ss);
     return mpf_launch_status("k_pair_overlap");
 }
 
@@ -1947,11 +2130,41 @@ extern "C" int mpf_warp_views_and_blend_next(const float *d_rgba, const MpfWarpV
                                                 d_src_u8_bgr_next, d_obj_mask_next, d_quads_next, d_quads_complement_next, d_cum_mask_next, S, H, W, nullptr, stream);
 }
 
+static int pair_launch_impl(const float *d_rgba, const MpfWarpView *views, const MpfViewSupport *supports, int n_views,
+                            const float *d_mpi_next, const float *d_img_next, const float *d_params_next, int P,
+                            float flow_clip, float *d_out_rgba_next, float *d_flows_next, uint8_t *d_src_u8_bgr_next,
+                            const float *d_obj_mask_next, float *d_quads_next, float *d_quads_complement_next,
+                            const float *d_cum_mask_next, unsigned *d_support_next, unsigned *d_support_complement_next, unsigned tag_next,
+                            int S, int H, int W, const MpfMergeArgs *merge_prev, void *stream);
+
 extern "C" int mpf_warp_views_blend_next_merge_prev(const float *d_rgba, const MpfWarpView *views, int n_views,
                                                     const float *d_mpi_next, const float *d_img_next, const float *d_params_next, int P,
                                                     float flow_clip, float *d_out_rgba_next, float *d_flows_next, uint8_t *d_src_u8_bgr_next,
                                                     const float *d_obj_mask_next, float *d_quads_next, float *d_quads_complement_next,
                                                     const float *d_cum_mask_next, int S, int H, int W, const MpfMergeArgs *merge_prev, void *stream)
+{
+    return pair_launch_impl(d_rgba, views, nullptr, n_views, d_mpi_next, d_img_next, d_params_next, P, flow_clip, d_out_rgba_next, d_flows_next, d_src_u8_bgr_next,
+                            d_obj_mask_next, d_quads_next, d_quads_complement_next, d_cum_mask_next, nullptr, nullptr, 0, S, H, W, merge_prev, stream);
+}
+
+extern "C" int mpf_warp_views_blend_next_merge_prev_support(const float *d_rgba, const MpfWarpView *views, const MpfViewSupport *supports, int n_views,
+                                                            const float *d_mpi_next, const float *d_img_next, const float *d_params_next, int P,
+                                                            float flow_clip, float *d_out_rgba_next, float *d_flows_next, uint8_t *d_src_u8_bgr_next,
+                                                            const float *d_obj_mask_next, float *d_quads_next, float *d_quads_complement_next,
+                                                            const float *d_cum_mask_next, uint32_t *d_support_next, uint32_t *d_support_complement_next,
+                                                            uint32_t tag_next, int S, int H, int W, const MpfMergeArgs *merge_prev, void *stream)
+{
+    return pair_launch_impl(d_rgba, views, supports, n_views, d_mpi_next, d_img_next, d_params_next, P, flow_clip, d_out_rgba_next, d_flows_next, d_src_u8_bgr_next,
+                            d_obj_mask_next, d_quads_next, d_quads_complement_next, d_cum_mask_next, d_support_next, d_support_complement_next, tag_next, S, H, W,
+                            merge_prev, stream);
+}
+
+static int pair_launch_impl(const float *d_rgba, const MpfWarpView *views, const MpfViewSupport *supports, int n_views,
+                            const float *d_mpi_next, const float *d_img_next, const float *d_params_next, int P,
+                            float flow_clip, float *d_out_rgba_next, float *d_flows_next, uint8_t *d_src_u8_bgr_next,
+                            const float *d_obj_mask_next, float *d_quads_next, float *d_quads_complement_next,
+                            const float *d_cum_mask_next, unsigned *d_support_next, unsigned *d_support_complement_next, unsigned tag_next,
+                            int S, int H, int W, const MpfMergeArgs *merge_prev, void *stream)
 {
     MpfMergeArgs mg;
     memset(&mg, 0, sizeof(mg));
@@ -2011,6 +2224,11 @@ extern "C" int mpf_warp_views_blend_next_merge_prev(const float *d_rgba, const M
     MPF_REQUIRE(P >= 0 && P <= 2 && (P == 0) == (d_flows_next == nullptr), "mpf_warp_views_and_blend_next: P must be 0..2, flows output iff P > 0");
     MPF_REQUIRE((d_quads_next == nullptr && d_quads_complement_next == nullptr) || d_obj_mask_next, "mpf_warp_views_and_blend_next: quads need d_obj_mask_next");
     MPF_REQUIRE(mpf_aligned16(d_quads_next) && mpf_aligned16(d_quads_complement_next), "mpf_warp_views_and_blend_next: quads must be 16-byte aligned");
+    MPF_REQUIRE((d_support_next == nullptr || d_quads_next) && (d_support_complement_next == nullptr || d_quads_complement_next),
+                "mpf_warp_views_and_blend_next: a support map needs its quads");
+    for (int v = 0; supports && v < n_views; ++v)          // the two halves of the launch are unordered: a map being written cannot be one being tested
+        MPF_REQUIRE(!supports[v].d_cells || (supports[v].d_cells != d_support_next && supports[v].d_cells != d_support_complement_next),
+                    "mpf_warp_views_and_blend_next: view %d tests a support map this launch writes", v);
     MpfViewSet vs;
     memset(&vs, 0, sizeof(vs));
     const bool has_mask = views[0].d_mask_quads != nullptr;
@@ -2025,13 +2243,14 @@ extern "C" int mpf_warp_views_blend_next_merge_prev(const float *d_rgba, const M
     const int64_t N = (int64_t)H * W;
     const MpfSbfArgs ac = { d_mpi_next, d_img_next, d_params_next, flow_clip, d_out_rgba_next, nullptr, nullptr, d_flows_next, (N + MPF_OVL_PX - 1) / MPF_OVL_PX, d_src_u8_bgr_next,
                             (d_quads_next || d_quads_complement_next) ? d_obj_mask_next : nullptr, reinterpret_cast<float4 *>(d_quads_next),
-                            reinterpret_cast<float4 *>(d_quads_complement_next), d_cum_mask_next, 4 * N, 3 * N };
+                            reinterpret_cast<float4 *>(d_quads_complement_next), d_cum_mask_next, 4 * N, 3 * N, d_support_next, d_support_complement_next, tag_next };
+    const MpfSupportSet ss = mpf_support_set(views, supports, n_views, has_mask);
     hipStream_t st = (hipStream_t)stream;
 #define MPF_OVL(HM, NLv)                                                                                                        \
     switch (P) {                                                                                                                \
-    case 0: return d_cum_mask_next ? launch_overlap<HM, NLv, 0, true>(d_rgba, vs, n_views, ac, S, H, W, st, mg) : launch_overlap<HM, NLv, 0, false>(d_rgba, vs, n_views, ac, S, H, W, st, mg); \
-    case 1: return d_cum_mask_next ? launch_overlap<HM, NLv, 1, true>(d_rgba, vs, n_views, ac, S, H, W, st, mg) : launch_overlap<HM, NLv, 1, false>(d_rgba, vs, n_views, ac, S, H, W, st, mg); \
-    default: return d_cum_mask_next ? launch_overlap<HM, NLv, 2, true>(d_rgba, vs, n_views, ac, S, H, W, st, mg) : launch_overlap<HM, NLv, 2, false>(d_rgba, vs, n_views, ac, S, H, W, st, mg); \
+    case 0: return d_cum_mask_next ? launch_overlap<HM, NLv, 0, true>(d_rgba, vs, n_views, ac, S, H, W, st, mg, ss) : launch_overlap<HM, NLv, 0, false>(d_rgba, vs, n_views, ac, S, H, W, st, mg, ss); \
+    case 1: return d_cum_mask_next ? launch_overlap<HM, NLv, 1, true>(d_rgba, vs, n_views, ac, S, H, W, st, mg, ss) : launch_overlap<HM, NLv, 1, false>(d_rgba, vs, n_views, ac, S, H, W, st, mg, ss); \
+    default: return d_cum_mask_next ? launch_overlap<HM, NLv, 2, true>(d_rgba, vs, n_views, ac, S, H, W, st, mg, ss) : launch_overlap<HM, NLv, 2, false>(d_rgba, vs, n_views, ac, S, H, W, st, mg, ss); \
     }
     if (S < 256) { if (has_mask) { MPF_OVL(true, 2) } else { MPF_OVL(false, 2) } }
     else         { if (has_mask) { MPF_OVL(true, 3) } else { MPF_OVL(false, 3) } }

@@ -81,11 +81,13 @@ def warp_params(H_src_tgt, K_inv, G, depth_S):
 @_on_device
 def src_blend_flow(mpi_S4HW, img_3HW, K_inv=None, depth_S=None, homs_tgt_src=None, flow_clip=200.0,
                    want_rgba=True, want_planar=False, want_tacc=False, out_rgba=None, out_flows=None,
-                   dparams=None, P=None, src_u8=None, obj_mask=None, quads=None, quads_complement=None, cum_mask=None):
+                   dparams=None, P=None, src_u8=None, obj_mask=None, quads=None, quads_complement=None, cum_mask=None,
+                   support=None, support_complement=None, tag=0):
     """Stage A + C.  homs_tgt_src: None or [P,S,3,3] CPU (P <= 2), or pass a pre-uploaded `dparams` + P.
     Fused by-products (preallocated outputs, optional): src_u8 [H,W,3] u8 BGR source frame; quads / quads_complement
     [H,W,4] = mask_quads(obj_mask, False / True).  cum_mask [S,H,W]: `mpi` is the RAW decoder output and the network's
-    activation epilogue (sigmoid / relu(x*cum_mask)+1e-4) is fused into this pass.  Returns dict(rgba, rgb_planar, tacc, flows)."""
+    activation epilogue (sigmoid / relu(x*cum_mask)+1e-4) is fused into this pass.  support / support_complement: the mask support maps of
+    quads / quads_complement (alloc_support_map) - their live cells get `tag` (mpf_src_blend_flow_support).  Returns dict(rgba, rgb_planar, tacc, flows)."""
     lib = _lib.load()
     mpi = _dev(mpi_S4HW, "mpi")
     S, C, H, W = mpi.shape
@@ -98,11 +100,15 @@ def src_blend_flow(mpi_S4HW, img_3HW, K_inv=None, depth_S=None, homs_tgt_src=Non
     planar = torch.empty((S, 3, H, W), dtype=_f32, device=mpi.device) if want_planar else None
     tacc = torch.empty((S, H, W), dtype=_f32, device=mpi.device) if want_tacc else None
     flows = out_flows if out_flows is not None else (torch.empty((P, 2, H, W), dtype=_f32, device=mpi.device) if P else None)
-    _lib.check(lib.mpf_src_blend_flow(_ptr(mpi), _ptr(img), _ptr(dparams), P, S, H, W, float(flow_clip), _ptr(rgba),
-                                      _ptr(planar), _ptr(tacc), _ptr(flows), _ptr(src_u8),
-                                      _ptr(_dev(obj_mask, "obj_mask").reshape(H, W)) if obj_mask is not None else None,
-                                      _ptr(quads), _ptr(quads_complement),
-                                      _ptr(_dev(cum_mask, "cum_mask")) if cum_mask is not None else None, _stream()), "mpf_src_blend_flow")
+    args = [_ptr(mpi), _ptr(img), _ptr(dparams), P, S, H, W, float(flow_clip), _ptr(rgba), _ptr(planar), _ptr(tacc), _ptr(flows), _ptr(src_u8),
+            _ptr(_dev(obj_mask, "obj_mask").reshape(H, W)) if obj_mask is not None else None, _ptr(quads), _ptr(quads_complement),
+            _ptr(_dev(cum_mask, "cum_mask")) if cum_mask is not None else None]
+    if support is not None or support_complement is not None:
+        _check_support_map(support, H, W, mpi.device)
+        _check_support_map(support_complement, H, W, mpi.device)
+        _lib.check(lib.mpf_src_blend_flow_support(*args, _ptr(support), _ptr(support_complement), int(tag), _stream()), "mpf_src_blend_flow_support")
+    else:
+        _lib.check(lib.mpf_src_blend_flow(*args, _stream()), "mpf_src_blend_flow")
     return dict(rgba=rgba, rgb_planar=planar, tacc=tacc, flows=flows)
 
 
@@ -113,6 +119,47 @@ def alloc_rgba_stack(S, H, W, device):
     n = S * H * W * 4
     store = torch.zeros(n + (W + 2) * 4, dtype=_f32, device=device)
     return store[:n].view(S, H, W, 4)
+
+
+def support_cells(H, W):
+    """(rows, columns) of a mask support map over an H x W frame (MPF_SUPPORT_CELLS)."""
+    return (H + _lib.SUPPORT_CELL_H - 1) // _lib.SUPPORT_CELL_H, (W + _lib.SUPPORT_CELL_W - 1) // _lib.SUPPORT_CELL_W
+
+
+@_on_device
+def alloc_support_map(H, W, device):
+    """A zeroed mask support map (include/mpiflow_hip.h, "mask support maps"): int32 [rows, columns], to be used with tags 1, 2, ..."""
+    return torch.zeros(support_cells(H, W), dtype=torch.int32, device=device)
+
+
+def _check_support_map(t, H, W, device):
+    assert t is None or (t.is_cuda and t.device == device and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == support_cells(H, W)), \
+        "a support map is a contiguous int32 tensor of shape support_cells(H, W) on the stack's device"
+
+
+def _support_array(views, H, W, device):
+    """views' optional `support` = (map, tag, thresh) -> MpfViewSupport array, or None when no view carries one"""
+    if not any(v.get("support") is not None for v in views):
+        return None
+    arr = (_lib.MpfViewSupport * len(views))()
+    for i, v in enumerate(views):
+        if v.get("support") is not None:
+            cells, tag, thresh = v["support"]
+            _check_support_map(cells, H, W, device)
+            arr[i] = _lib.MpfViewSupport(cells.data_ptr(), int(tag), float(thresh))
+    return arr
+
+
+@_on_device
+def support_dead_tiles(views, S, H, W):
+    """The device's own skip decision (mpf_support_dead_tiles): uint8 [len(views), ceil(H/8), ceil(W/32)], 1 = the tile is not rendered.
+    views as for warp_composite_views, each with `support` = (map, tag, thresh) or without."""
+    lib = _lib.load()
+    dev = views[0]["dparams"].device
+    sup = _support_array(views, H, W, dev) or (_lib.MpfViewSupport * len(views))()
+    dead = torch.empty((len(views), (H + 7) // 8, (W + 31) // 32), dtype=torch.uint8, device=dev)
+    _lib.check(lib.mpf_support_dead_tiles(_view_array(views, dev), sup, len(views), S, H, W, _ptr(dead), _stream()), "mpf_support_dead_tiles")
+    return dead
 
 
 @_on_device
@@ -221,7 +268,8 @@ def src_flow_hard(sigma_or_stack, K_inv, depth_S, homs_tgt_src, flow_clip=200.0)
 def warp_composite_views(rgba, views, interleaved=2):
     """Stage B for several views of one interleaved stack in ONE launch (mpf_warp_composite_views): the stack crosses the HBM
     interface once instead of once per view.  views: list of dicts(dparams=, quads= | None, out=dict(rgb, objmask?, depth?,
-    tgt_mask?, rgb_u8?)) - every buffer preallocated.  Bit-identical to len(views) warp_composite calls."""
+    tgt_mask?, rgb_u8?)) - every buffer preallocated.  Bit-identical to len(views) warp_composite calls.  A view with
+    support=(map, tag, thresh) skips the tiles whose mask taps are all zero (mpf_warp_composite_views_support; output contract: include/mpiflow_hip.h)."""
     lib = _lib.load()
     a = _dev(rgba, "rgba")
     S, H, W, C = a.shape
@@ -236,7 +284,11 @@ def warp_composite_views(rgba, views, interleaved=2):
             assert t is None or (t.is_cuda and t.is_contiguous() and t.device == a.device)
         arr[i] = _lib.MpfWarpView(v["dparams"].data_ptr(), q.data_ptr() if q is not None else None, o["rgb"].data_ptr(),
                                   *[(o[k].data_ptr() if o.get(k) is not None else None) for k in ("depth", "objmask", "tgt_mask", "rgb_u8")])
-    _lib.check(lib.mpf_warp_composite_views(_ptr(a), int(interleaved), arr, len(views), S, H, W, _stream()), "mpf_warp_composite_views")
+    sup = _support_array(views, H, W, a.device)
+    if sup is not None:
+        _lib.check(lib.mpf_warp_composite_views_support(_ptr(a), int(interleaved), arr, sup, len(views), S, H, W, _stream()), "mpf_warp_composite_views_support")
+    else:
+        _lib.check(lib.mpf_warp_composite_views(_ptr(a), int(interleaved), arr, len(views), S, H, W, _stream()), "mpf_warp_composite_views")
     return [v["out"] for v in views]
 
 
@@ -255,12 +307,13 @@ def _view_array(views, device):
 @_on_device
 def warp_views_and_blend_next(rgba, views, mpi_next, img_next, dparams_next, P, out_rgba_next, out_flows_next=None, flow_clip=200.0,
                               src_u8_next=None, obj_mask_next=None, quads_next=None, quads_complement_next=None, cum_mask_next=None,
-                              merge_prev=None):
+                              merge_prev=None, support_next=None, support_complement_next=None, tag_next=0):
     """Stage B of one image (all `views` of the tail-padded stack `rgba`, as warp_composite_views) and Stage A+C of the NEXT image
     (as src_blend_flow with preallocated outputs) in ONE launch whose grid interleaves the two kinds of workgroups
     (mpf_warp_views_and_blend_next).  Bit-identical to the two separate calls; every *_next buffer must be distinct from what the
     views read or write.  merge_prev: merge_args(...) of an EARLIER pair, merged by the Stage A+C role as a per-pixel prologue
-    (mpf_warp_views_blend_next_merge_prev); its flows may be `out_flows_next` itself."""
+    (mpf_warp_views_blend_next_merge_prev); its flows may be `out_flows_next` itself.  Views with support=(map, tag, thresh) skip their dead
+    tiles; support_next / support_complement_next are the next pair's maps, written with tag_next (mpf_warp_views_blend_next_merge_prev_support)."""
     lib = _lib.load()
     a = _dev(rgba, "rgba")
     S, H, W, C = a.shape
@@ -273,11 +326,20 @@ def warp_views_and_blend_next(rgba, views, mpi_next, img_next, dparams_next, P, 
     arr = _view_array(views, a.device)
     om = _dev(obj_mask_next, "obj_mask_next").reshape(H, W) if obj_mask_next is not None else None
     cm = _dev(cum_mask_next, "cum_mask_next") if cum_mask_next is not None else None
-    _lib.check(lib.mpf_warp_views_blend_next_merge_prev(_ptr(a), arr, len(views), _ptr(mpi), _ptr(img), _ptr(dparams_next), int(P), float(flow_clip),
-                                                        _ptr(out_rgba_next), _ptr(out_flows_next), _ptr(src_u8_next), _ptr(om), _ptr(quads_next),
-                                                        _ptr(quads_complement_next), _ptr(cm), S, H, W,
-                                                        ctypes.byref(merge_prev) if merge_prev is not None else None, _stream()),
-               "mpf_warp_views_blend_next_merge_prev")
+    sup = _support_array(views, H, W, a.device)
+    mp = ctypes.byref(merge_prev) if merge_prev is not None else None
+    if sup is not None or support_next is not None or support_complement_next is not None:
+        _check_support_map(support_next, H, W, a.device)
+        _check_support_map(support_complement_next, H, W, a.device)
+        _lib.check(lib.mpf_warp_views_blend_next_merge_prev_support(
+            _ptr(a), arr, sup, len(views), _ptr(mpi), _ptr(img), _ptr(dparams_next), int(P), float(flow_clip), _ptr(out_rgba_next), _ptr(out_flows_next),
+            _ptr(src_u8_next), _ptr(om), _ptr(quads_next), _ptr(quads_complement_next), _ptr(cm), _ptr(support_next), _ptr(support_complement_next),
+            int(tag_next), S, H, W, mp, _stream()), "mpf_warp_views_blend_next_merge_prev_support")
+    else:
+        _lib.check(lib.mpf_warp_views_blend_next_merge_prev(_ptr(a), arr, len(views), _ptr(mpi), _ptr(img), _ptr(dparams_next), int(P), float(flow_clip),
+                                                            _ptr(out_rgba_next), _ptr(out_flows_next), _ptr(src_u8_next), _ptr(om), _ptr(quads_next),
+                                                            _ptr(quads_complement_next), _ptr(cm), S, H, W, mp, _stream()),
+                   "mpf_warp_views_blend_next_merge_prev")
     return [v["out"] for v in views]
 
 

@@ -217,16 +217,23 @@ class OverlappedPairRenderer(_PairHostSide):
     (mpf_warp_views_blend_next_merge_prev) - the thread that merges a pixel is the one that later overwrites that pixel's flows in the
     slot the two pairs share, so no further buffering is needed.  The stream is then ONE launch per pair and nothing else; push() hands back
     the pair enqueued TWO calls earlier, `out` of a pair must stay untouched for two further push() calls (three alternating buffers), and
-    flush() returns the last two pairs."""
+    flush() returns the last two pairs.
 
-    def __init__(self, S, H, W, device, thresh=MASK_THRESH, merge_in_launch=False):
+    skip_dead_tiles (default): Stage B does not render the tiles whose object-mask taps are all zero - the merge never reads a view's rgb there
+    (include/mpiflow_hip.h, "mask support maps").  Each slot holds the support maps of its two quad buffers, written by the pair's Stage A+C
+    with the pair's own tag (a counter), so nothing is ever cleared.  The views are internal to the renderer; the handed-back products are
+    bit-identical with and without it.  Views rendered with thresh <= 0 take the full render (the launcher decides)."""
+
+    def __init__(self, S, H, W, device, thresh=MASK_THRESH, merge_in_launch=False, skip_dead_tiles=True):
         self.S, self.H, self.W, self.device, self.thresh = S, H, W, torch.device(device), thresh
+        self.skip_dead_tiles, self._tag = skip_dead_tiles, 0
         self.merge_in_launch, self._merging, self.chain_ordered = merge_in_launch, None, True
         self.guard_unconsumed = True                                 # see _start_chain_unordered
         f32, dev = torch.float32, self.device
         self.slots = [dict(rgba=ops.alloc_rgba_stack(S, H, W, dev), flows=torch.empty((2, 2, H, W), dtype=f32, device=dev),
                            quads=[torch.empty((H, W, 4), dtype=f32, device=dev) for _ in range(2)],
                            src_u8=torch.empty((H, W, 3), dtype=torch.uint8, device=dev),
+                           support=[ops.alloc_support_map(H, W, dev) for _ in range(2)],
                            views=[dict(rgb=torch.empty((3, H, W), dtype=f32, device=dev), objmask=torch.empty((H, W), dtype=f32, device=dev),
                                        rgb_u8=torch.empty((H, W, 3), dtype=torch.uint8, device=dev)) for _ in range(2)])
                       for _ in range(2)]
@@ -299,8 +306,18 @@ class OverlappedPairRenderer(_PairHostSide):
         except Exception:                                             # noqa: BLE001 - interpreter shutdown
             pass
 
-    def _views(self, slot, prep):
-        return [dict(dparams=prep["warp"][v], quads=slot["quads"][v], out=slot["views"][v]) for v in range(2)]
+    def _views(self, pend):
+        slot, prep = pend["slot"], pend["prep"]
+        skip = self.skip_dead_tiles and not pend.get("observed")      # see pending_slot
+        sup = [(slot["support"][v], pend["tag"], self.thresh) if skip else None for v in range(2)]
+        return [dict(dparams=prep["warp"][v], quads=slot["quads"][v], out=slot["views"][v], support=sup[v]) for v in range(2)]
+
+    def _support_of(self, slot, tag):
+        """keyword arguments of the Stage A+C side: the slot's two support maps and the tag of the pair being written"""
+        if not self.skip_dead_tiles:
+            return {}, {}
+        return (dict(support=slot["support"][0], support_complement=slot["support"][1], tag=tag),
+                dict(support_next=slot["support"][0], support_complement_next=slot["support"][1], tag_next=tag))
 
     def _start_chain(self, slot, moving):
         """ordered chain, right behind the launch whose Stage A+C role wrote slot['src_u8']: the pair's moving-object chain, on the side
@@ -388,9 +405,9 @@ class OverlappedPairRenderer(_PairHostSide):
         ops.merge(*self._merge_operands(pend), self.thresh, out=self._out_of(pend), obj_mask_stride=4)
         return self._handed_back(pend)
 
-    def _blend_alone(self, slot, mpi, image, prep, obj_mask, cum_mask):
+    def _blend_alone(self, slot, mpi, image, prep, obj_mask, cum_mask, tag):
         ops.src_blend_flow(mpi, image, out_rgba=slot["rgba"], out_flows=slot["flows"], dparams=prep["blend"], P=2, src_u8=slot["src_u8"],
-                           obj_mask=obj_mask, quads=slot["quads"][0], quads_complement=slot["quads"][1], cum_mask=cum_mask)
+                           obj_mask=obj_mask, quads=slot["quads"][0], quads_complement=slot["quads"][1], cum_mask=cum_mask, **self._support_of(slot, tag)[0])
 
     def push(self, mpi, image, prep, obj_mask, out=None, cum_mask=None, moving=None, moving_ready=None):
         """Enqueue one pair (prep from prepare(K, disparity, [G_cam, G_dyn]); view 0 samples obj_mask, view 1 its complement).
@@ -404,21 +421,22 @@ class OverlappedPairRenderer(_PairHostSide):
         obj_mask = obj_mask.reshape(self.H, self.W)
         if obj_mask.dtype != torch.float32 or not obj_mask.is_contiguous():
             obj_mask = obj_mask.to(torch.float32).contiguous()
-        new = dict(slot=slot, prep=prep, out=out, moving=self._start_chain_unordered(image, moving, moving_ready))
+        self._tag = self._tag % 0x7FFFFFFF + 1                       # 1, 2, ...: never 0, what a fresh map holds
+        new = dict(slot=slot, prep=prep, out=out, tag=self._tag, moving=self._start_chain_unordered(image, moving, moving_ready))
         self._wait_chain_of(slot)                                    # this slot's source frame is about to be rewritten
         pend = self._pending
         if pend is None:
-            self._blend_alone(slot, mpi, image, prep, obj_mask, cum_mask)
+            self._blend_alone(slot, mpi, image, prep, obj_mask, cum_mask, new["tag"])
         elif not self.fusable:
-            ops.warp_composite_views(pend["slot"]["rgba"], self._views(pend["slot"], pend["prep"]), interleaved=2)
-            self._blend_alone(slot, mpi, image, prep, obj_mask, cum_mask)
+            ops.warp_composite_views(pend["slot"]["rgba"], self._views(pend), interleaved=2)
+            self._blend_alone(slot, mpi, image, prep, obj_mask, cum_mask, new["tag"])
         else:
             mg, self._merging = self._merging, None
             mp = ops.merge_args(*self._merge_operands(mg), self.thresh, self._out_of(mg), obj_mask_stride=4) if mg is not None else None
             launch = lambda: ops.warp_views_and_blend_next(                                                   # noqa: E731
-                pend["slot"]["rgba"], self._views(pend["slot"], pend["prep"]), mpi, image, prep["blend"], 2, slot["rgba"],
+                pend["slot"]["rgba"], self._views(pend), mpi, image, prep["blend"], 2, slot["rgba"],
                 out_flows_next=slot["flows"], src_u8_next=slot["src_u8"], obj_mask_next=obj_mask, quads_next=slot["quads"][0],
-                quads_complement_next=slot["quads"][1], cum_mask_next=cum_mask, merge_prev=mp)
+                quads_complement_next=slot["quads"][1], cum_mask_next=cum_mask, merge_prev=mp, **self._support_of(slot, new["tag"])[1])
             if self.on_fused is not None:
                 self.on_fused(launch)
             else:
@@ -443,7 +461,7 @@ class OverlappedPairRenderer(_PairHostSide):
         self._pending = self._merging = None
         res = []
         if pend is not None:
-            ops.warp_composite_views(pend["slot"]["rgba"], self._views(pend["slot"], pend["prep"]), interleaved=2)
+            ops.warp_composite_views(pend["slot"]["rgba"], self._views(pend), interleaved=2)
         for p in (mg, pend):
             if p is not None:
                 res.append(self._finish(p))
@@ -454,7 +472,12 @@ class OverlappedPairRenderer(_PairHostSide):
 
     @property
     def pending_slot(self):
-        return None if self._pending is None else self._pending["slot"]
+        """The slot (buffers) of the pair enqueued last, whose Stage B has not been issued yet.  Handing it out makes that pair's views visible to
+        the caller, so its Stage B renders every tile: views nobody but the merge reads may have their dead tiles zeroed (skip_dead_tiles)."""
+        if self._pending is None:
+            return None
+        self._pending["observed"] = True
+        return self._pending["slot"]
 
 
 def hard_flows(mpi_S4HW, disparity_S, K, poses, generic=False):
