@@ -439,6 +439,44 @@ typedef struct MpfCorrArgs {
 int mpf_corr_lookup(const MpfCorrArgs *a, void *stream);
 int mpf_corr_lookup_backward(const MpfCorrArgs *a, void *stream);
 
+/* RAFT's all-pairs correlation block (CorrBlock, RAFT/core/corr.py:12-60): the pyramid of the volume, the lookup of every level in one launch, and
+ * both gradients.  The three GEMMs (raw = fmap1^T fmap2; grad_fmap1, grad_fmap2 from the folded gradient) are the caller's.
+ *   level[i]  f32 [B*H*W, Hl[i], Wl[i]], Hl[i] = H >> i, Wl[i] = W >> i (chained 2 x 2 average pooling with floor sizes): ROW p of every level is
+ *             query pixel p = (b*H + y)*W + x against all of frame 2.  Either the pyramid itself or its gradient, see the calls.
+ *   coords    f32 [B,2,H,W], (x, y) in pixels of level 0;  rd = 2 * radius + 1
+ *   out[b, i*rd*rd + a*rd + c, y, x] = bilinear(level[i][p], X, Y),   X = coords[b,0,y,x] / 2^i + (a - radius),  Y = coords[b,1,y,x] / 2^i + (c - radius)
+ *             (the FIRST window index moves x); bilinear as for mpf_corr_lookup: four integer taps, a tap outside the level contributes 0.
+ * mpf_corr_pyramid                 level[0] holds the raw product on entry: divides it by norm IN PLACE and writes level[1 .. levels-1]
+ *                                  (torch's avg_pool2d: ((a00 + a01) + a10) + a11, times 1/4; each level from the rounded one before it).
+ * mpf_corr_volume_lookup           reads level[], writes out f32 [B, levels*rd*rd, H, W]; one launch for all levels; each pixel reads the (rd+1)^2
+ *                                  patch of its own row once per level.
+ * mpf_corr_volume_lookup_backward  reads out as the cotangent; ADDS its gradient into level[] (the caller's gradient pyramid, zeroed once by the
+ *                                  caller, shared by any number of lookups).  One thread owns every entry it updates (a lookup of pixel p touches
+ *                                  row p only): plain loads and stores, no atomics, bit-identical from run to run.  Calls that share a gradient
+ *                                  pyramid must be ordered (one stream, or events).  No gradient for coords.
+ * mpf_corr_pyramid_backward        level[] holds the gradient pyramid: folds it into the gradient of the raw product, IN PLACE in level[0]:
+ *                                  level[0][p,y,x] = (g0 + (g1[y>>1, x>>1] + (g2[y>>2, x>>2] + ...) / 4) / 4) / norm, a level taking part where it covers
+ *                                  (y, x) (floor pooling drops a last odd row / column).  level[1 ..] are read only.
+ * coords are UNTRUSTED, as for mpf_corr_lookup: NaN, +-inf and far-out values give exactly 0 and add nothing to the gradient; they are clamped in
+ * floating point before the conversion to int and no value makes a kernel touch memory outside its buffers.  Row offsets are 64-bit (B*H*W*H*W
+ * may exceed 2^31).  fp32 throughout.  levels 1..MPF_CORR_MAX_LEVELS; every level at least 2 x 2.  Lookup calls: radius 1..8, level[] 4-byte
+ * aligned.  Pyramid calls: level[] 16-byte aligned (level 0 moves 16 bytes per lane where W allows), norm finite and not 0, and
+ * W * 2^(levels-1) <= 12288 (mpf_corr_pyramid pools one strip of 2^(levels-1) image rows in LDS; mpf_corr_pyramid_backward uses no LDS but takes
+ * the same shapes and no others: a pyramid that cannot be built has no gradient).  Validated before anything is launched. */
+typedef struct MpfCorrVolumeArgs {
+    float *level[MPF_CORR_MAX_LEVELS];       /* the pyramid (pyramid: written; lookup: read) or its gradient (lookup backward: added to; pyramid backward: folded) */
+    const float *coords;                     /* lookup calls */
+    float *out;                              /* lookup: written;  lookup backward: the cotangent, read */
+    int B, H, W;
+    int Hl[MPF_CORR_MAX_LEVELS], Wl[MPF_CORR_MAX_LEVELS];
+    int radius, levels;
+    float norm;                              /* pyramid calls; RAFT: sqrt(C) in float32 */
+} MpfCorrVolumeArgs;
+int mpf_corr_pyramid(const MpfCorrVolumeArgs *a, void *stream);
+int mpf_corr_volume_lookup(const MpfCorrVolumeArgs *a, void *stream);
+int mpf_corr_volume_lookup_backward(const MpfCorrVolumeArgs *a, void *stream);
+int mpf_corr_pyramid_backward(const MpfCorrVolumeArgs *a, void *stream);
+
 /* RAFT's convex upsampling (RAFT.upsample_flow, RAFT/core/raft.py:72-83) and the per-prediction term of its sequence loss (RAFT/train.py:47-72),
  * fused.  All tensors f32, contiguous:
  *   flow  [N,2,H,W];  mask  [N,576,H,W], channel k*64 + i*8 + j = tap k = ky*3 + kx, sub-row i, sub-column j

@@ -113,6 +113,12 @@ class MpfCorrArgs(ctypes.Structure):
                 ("radius", c_i), ("levels", c_i), ("scale", c_f), ("plain", c_i)]
 
 
+class MpfCorrVolumeArgs(ctypes.Structure):
+    """struct MpfCorrVolumeArgs of include/mpiflow_hip.h: RAFT's all-pairs correlation block: pyramid, lookup and both gradients (device pointers)."""
+    _fields_ = [("level", c_p * CORR_MAX_LEVELS), ("coords", c_p), ("out", c_p), ("B", c_i), ("H", c_i), ("W", c_i),
+                ("Hl", c_i * CORR_MAX_LEVELS), ("Wl", c_i * CORR_MAX_LEVELS), ("radius", c_i), ("levels", c_i), ("norm", c_f)]
+
+
 class MpfUpsampleArgs(ctypes.Structure):
     """struct MpfUpsampleArgs of include/mpiflow_hip.h: RAFT's convex upsampling and its loss term, forward and gradient (device pointers)."""
     _fields_ = [("flow", c_p), ("mask", c_p), ("out", c_p), ("flow_gt", c_p), ("valid", c_p), ("g", c_p), ("term", c_p), ("metrics", c_p),
@@ -164,6 +170,10 @@ SIGNATURES = {
     "mpf_photometric_pairs": (c_i, [ctypes.POINTER(MpfPhotoSample), c_i, c_i, c_i, c_p, c_sz, c_p]),
     "mpf_corr_lookup": (c_i, [ctypes.POINTER(MpfCorrArgs), c_p]),
     "mpf_corr_lookup_backward": (c_i, [ctypes.POINTER(MpfCorrArgs), c_p]),
+    "mpf_corr_pyramid": (c_i, [ctypes.POINTER(MpfCorrVolumeArgs), c_p]),
+    "mpf_corr_volume_lookup": (c_i, [ctypes.POINTER(MpfCorrVolumeArgs), c_p]),
+    "mpf_corr_volume_lookup_backward": (c_i, [ctypes.POINTER(MpfCorrVolumeArgs), c_p]),
+    "mpf_corr_pyramid_backward": (c_i, [ctypes.POINTER(MpfCorrVolumeArgs), c_p]),
     "mpf_upsample_workspace": (c_sz, [c_i, c_i, c_i, c_i]),
     "mpf_upsample_flow": (c_i, [ctypes.POINTER(MpfUpsampleArgs), c_p]),
     "mpf_upsample_flow_backward": (c_i, [ctypes.POINTER(MpfUpsampleArgs), c_p]),

@@ -16,10 +16,11 @@
 //                  first every load (sum into grad_fmap1's accumulator), then every atomic, so that no load waits behind an atomic.
 // k_corr_plain     the formula as it stands, one thread per output entry (MpfCorrArgs.plain).
 //
-// Untrusted coordinates: corr_axis() is the only place a coordinate becomes an integer.  It compares in floating point first (NaN fails
+// Untrusted coordinates: corr_axis() (mpf_corr_common.h) is the only place a coordinate becomes an integer.  It compares in floating point first (NaN fails
 // both comparisons), so the integer it returns lies in [-(2r+2), n+1] whatever the input, and every grid point is tested against the level's
 // bounds before its address is formed.
 #include "mpf_common.h"
+#include "mpf_corr_common.h"
 
 #define CORR_TILE 16             // query pixels per block of k_corr_forward
 #define CORR_THREADS 256
@@ -38,31 +39,6 @@ struct CorrDev {
     int radius, levels;
     float scale;
 };
-
-// first grid index of the window along one axis and the fraction shared by its taps; n = the level's extent along the axis
-__device__ __forceinline__ void corr_axis(float c, float inv, int n, int r, int &i0, float &frac)
-{
-    const float v = c * inv;                                 // exact: inv is a power of two
-    const float fl = floorf(v);
-    if (fl >= (float)(-(r + 2)) && fl <= (float)(n + r + 1)) {
-        i0 = (int)fl - r;
-        frac = v - fl;
-    } else {                                                 // NaN, +-inf, or no tap can be inside: the window ends at -1
-        i0 = -(2 * r + 2);
-        frac = 0.0f;
-    }
-}
-
-__device__ __forceinline__ float corr_blend(float d00, float d01, float d10, float d11, float fx, float fy)
-{
-    // d[y][x]; the four bilinear weights, each product rounded
-    const float gx = 1.0f - fx, gy = 1.0f - fy;
-    float v = (gx * gy) * d00;
-    v = fmaf(fx * gy, d01, v);
-    v = fmaf(gx * fy, d10, v);
-    v = fmaf(fx * fy, d11, v);
-    return v;
-}
 
 __global__ __launch_bounds__(CORR_THREADS) void k_corr_forward(const CorrDev a)
 {

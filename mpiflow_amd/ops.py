@@ -25,7 +25,10 @@ def _on_device(fn):
     @functools.wraps(fn)
     def wrapped(*args, **kwargs):
         dev = None
-        for a in list(args) + list(kwargs.values()):
+        flat = []
+        for a in list(args) + list(kwargs.values()):                 # a list of tensors (a pyramid) counts as its tensors
+            flat.extend(a if isinstance(a, (list, tuple)) else [a])
+        for a in flat:
             if isinstance(a, torch.Tensor) and a.is_cuda:
                 dev = a.device
                 break
@@ -699,18 +702,21 @@ def photometric_pairs(samples, out=None):
     return out
 
 
-def _corr_tensor(t, name, ndim):
-    """RAFT's correlation lookup takes its tensors as they are: no silent copy, cast or move."""
+def _corr_tensor(t, name, ndim, who="corr_lookup", device_last=False):
+    """RAFT's correlation lookups take their tensors as they are: no silent copy, cast or move.  device_last: dtype and layout are judged
+    before the device, so that each refusal can be had without a GPU."""
     if not isinstance(t, torch.Tensor):
-        raise _lib.MpiFlowHipError("corr_lookup: %s must be a torch.Tensor (got %s)" % (name, type(t).__name__))
-    if not t.is_cuda:
-        raise _lib.MpiFlowHipError("corr_lookup: %s must live on the GPU (got %s); mpiflow_amd has no CPU path" % (name, t.device))
+        raise _lib.MpiFlowHipError("%s: %s must be a torch.Tensor (got %s)" % (who, name, type(t).__name__))
+    if not t.is_cuda and not device_last:
+        raise _lib.MpiFlowHipError("%s: %s must live on the GPU (got %s); mpiflow_amd has no CPU path" % (who, name, t.device))
     if t.dtype != _f32:
-        raise _lib.MpiFlowHipError("corr_lookup: %s must be float32 (got %s)" % (name, t.dtype))
+        raise _lib.MpiFlowHipError("%s: %s must be float32 (got %s)" % (who, name, t.dtype))
     if t.dim() != ndim:
-        raise _lib.MpiFlowHipError("corr_lookup: %s must have %d dimensions (got shape %s)" % (name, ndim, tuple(t.shape)))
+        raise _lib.MpiFlowHipError("%s: %s must have %d dimensions (got shape %s)" % (who, name, ndim, tuple(t.shape)))
     if not t.is_contiguous():
-        raise _lib.MpiFlowHipError("corr_lookup: %s must be contiguous" % name)
+        raise _lib.MpiFlowHipError("%s: %s must be contiguous" % (who, name))
+    if not t.is_cuda:
+        raise _lib.MpiFlowHipError("%s: %s must live on the GPU (got %s); mpiflow_amd has no CPU path" % (who, name, t.device))
     return t
 
 
@@ -774,6 +780,127 @@ def corr_lookup_backward(fmap1_nhwc, f2_levels_nhwc, coords, grad_out, radius, s
         a.grad_f2[i] = t.data_ptr()
     _lib.check(lib.mpf_corr_lookup_backward(ctypes.byref(a), _stream()), "mpf_corr_lookup_backward")
     return g1, g2
+
+
+def _corr_volume_tensor(t, name, ndim, who):
+    """dtype and layout of one tensor of the all-pairs calls, taken as it is: no silent copy or cast.  The device is judged by
+    _corr_volume_args, after the shapes."""
+    if not isinstance(t, torch.Tensor):
+        raise _lib.MpiFlowHipError("%s: %s must be a torch.Tensor (got %s)" % (who, name, type(t).__name__))
+    if t.dtype != _f32:
+        raise _lib.MpiFlowHipError("%s: %s must be float32 (got %s)" % (who, name, t.dtype))
+    if t.dim() != ndim:
+        raise _lib.MpiFlowHipError("%s: %s must have %d dimensions (got shape %s)" % (who, name, ndim, tuple(t.shape)))
+    if not t.is_contiguous():
+        raise _lib.MpiFlowHipError("%s: %s must be contiguous" % (who, name))
+    return t
+
+
+def _corr_volume_frame(level0, num_levels, who):
+    """(N, H, W) of level 0 [N, H, W]: N = B * H * W rows, every level of the pooled pyramid at least 2 x 2"""
+    N, H, W = level0.shape
+    if H * W == 0 or N == 0 or N % (H * W):
+        raise _lib.MpiFlowHipError("%s: level 0 %s must hold B * H * W rows of H x W" % (who, tuple(level0.shape)))
+    if min(H, W) < 2 ** num_levels:
+        raise _lib.MpiFlowHipError("%s: H, W = %d, %d must be at least 2^num_levels = %d (every level at least 2 x 2)" % (who, H, W, 2 ** num_levels))
+    return N, H, W
+
+
+def _corr_volume_args(levels, who, norm=None, coords=None, radius=None, out=None, out_name="out"):
+    """MpfCorrVolumeArgs for a pyramid (or its gradient): levels[i] [N, H >> i, W >> i] with N = B*H*W rows, for a pyramid call (norm) or a
+    lookup call (coords [B,2,H,W], radius, and out / grad_out [B, L*(2r+1)^2, H, W] if the caller has one).  The C ABI sees bare pointers:
+    these comparisons are what ties every tensor's real size to what the kernels index.  Order: dtype and layout, then every shape, the
+    device last (a wrong shape is reported as such wherever the tensors live)."""
+    levels = list(levels)
+    if not 1 <= len(levels) <= _lib.CORR_MAX_LEVELS:
+        raise _lib.MpiFlowHipError("%s: num_levels must be 1..%d (got %d)" % (who, _lib.CORR_MAX_LEVELS, len(levels)))
+    tensors = [("levels[%d]" % i, _corr_volume_tensor(t, "levels[%d]" % i, 3, who)) for i, t in enumerate(levels)]
+    N, H, W = _corr_volume_frame(levels[0], len(levels), who)
+    a = _lib.MpfCorrVolumeArgs()
+    for i, t in enumerate(levels):
+        if tuple(t.shape) != (N, H >> i, W >> i):
+            raise _lib.MpiFlowHipError("%s: levels[%d] must be %s, level %d of a pooled pyramid of %d rows of %d x %d (got %s)"
+                                       % (who, i, (N, H >> i, W >> i), i, N, H, W, tuple(t.shape)))
+        a.level[i], a.Hl[i], a.Wl[i] = t.data_ptr(), H >> i, W >> i
+    a.B, a.H, a.W, a.levels = N // (H * W), H, W, len(levels)
+    if coords is None:
+        a.norm = float(norm)
+    else:
+        if not 1 <= int(radius) <= 8:
+            raise _lib.MpiFlowHipError("%s: radius must be 1..8 (got %s)" % (who, radius))
+        co = _corr_volume_tensor(coords, "coords", 4, who)
+        if tuple(co.shape) != (a.B, 2, H, W):
+            raise _lib.MpiFlowHipError("%s: coords must be [B,2,H,W] = %s for %d rows of %d x %d (got %s)" % (who, (a.B, 2, H, W), N, H, W, tuple(co.shape)))
+        tensors.append(("coords", co))
+        a.coords, a.radius = co.data_ptr(), int(radius)
+        if out is not None:
+            rd = 2 * int(radius) + 1
+            shape = (a.B, len(levels) * rd * rd, H, W)
+            if tuple(_corr_volume_tensor(out, out_name, 4, who).shape) != shape:
+                raise _lib.MpiFlowHipError("%s: %s must be %s (got %s)" % (who, out_name, shape, tuple(out.shape)))
+            tensors.append((out_name, out))
+            a.out = out.data_ptr()
+    for name, t in tensors:
+        if not t.is_cuda:
+            raise _lib.MpiFlowHipError("%s: %s must live on the GPU (got %s); mpiflow_amd has no CPU path" % (who, name, t.device))
+        if t.device != levels[0].device:
+            raise _lib.MpiFlowHipError("%s: %s is on %s, levels[0] on %s" % (who, name, t.device, levels[0].device))
+    return a, levels
+
+
+@_on_device
+def corr_pyramid(raw, num_levels, norm):
+    """mpf_corr_pyramid: raw [B*H*W, H, W], the product fmap1^T fmap2 (row p: query pixel p against all of frame 2) -> the list of num_levels
+    levels [B*H*W, H >> i, W >> i] of CorrBlock's pyramid.  Level 0 IS raw, divided by `norm` (RAFT: sqrt(C) in float32) in place; the other
+    levels are new.  float32, contiguous, on the GPU, or MpiFlowHipError.  Asynchronous on the current stream."""
+    lib = _lib.load()
+    raw = _corr_volume_tensor(raw, "raw", 3, "corr_pyramid")
+    if not 1 <= int(num_levels) <= _lib.CORR_MAX_LEVELS:
+        raise _lib.MpiFlowHipError("corr_pyramid: num_levels must be 1..%d (got %s)" % (_lib.CORR_MAX_LEVELS, num_levels))
+    N, H, W = _corr_volume_frame(raw, int(num_levels), "corr_pyramid")
+    if not raw.is_cuda:
+        raise _lib.MpiFlowHipError("corr_pyramid: raw must live on the GPU (got %s); mpiflow_amd has no CPU path" % raw.device)
+    levels = [raw] + [torch.empty((N, H >> i, W >> i), dtype=_f32, device=raw.device) for i in range(1, int(num_levels))]
+    a, levels = _corr_volume_args(levels, "corr_pyramid", norm=norm)
+    _lib.check(lib.mpf_corr_pyramid(ctypes.byref(a), _stream()), "mpf_corr_pyramid")
+    return levels
+
+
+@_on_device
+def corr_volume_lookup(levels, coords, radius, out=None):
+    """mpf_corr_volume_lookup: CorrBlock's lookup, every level in one launch.  levels: corr_pyramid's result, coords [B,2,H,W] (x, y; any value
+    is legal, non-finite ones give 0) -> [B, L*(2r+1)^2, H, W].  Asynchronous on the current stream."""
+    lib = _lib.load()
+    a, levels = _corr_volume_args(levels, "corr_volume_lookup", coords=coords, radius=radius, out=out)
+    if out is None:
+        rd = 2 * int(radius) + 1
+        out = torch.empty((a.B, len(levels) * rd * rd, a.H, a.W), dtype=_f32, device=coords.device)
+        a.out = out.data_ptr()
+    _lib.check(lib.mpf_corr_volume_lookup(ctypes.byref(a), _stream()), "mpf_corr_volume_lookup")
+    return out
+
+
+@_on_device
+def corr_volume_lookup_backward(grad_levels, coords, grad_out, radius):
+    """mpf_corr_volume_lookup_backward: ADDS the gradient of one lookup with the cotangent grad_out [B, L*(2r+1)^2, H, W] into grad_levels, a
+    gradient pyramid shaped like corr_pyramid's result that the caller zeroed once and may share between lookups.  No atomics: bit-identical
+    from run to run.  Returns grad_levels.  Asynchronous on the current stream."""
+    lib = _lib.load()
+    if grad_out is None:
+        raise _lib.MpiFlowHipError("corr_volume_lookup_backward: grad_out must be a torch.Tensor (got NoneType)")
+    a, grad_levels = _corr_volume_args(grad_levels, "corr_volume_lookup_backward", coords=coords, radius=radius, out=grad_out, out_name="grad_out")
+    _lib.check(lib.mpf_corr_volume_lookup_backward(ctypes.byref(a), _stream()), "mpf_corr_volume_lookup_backward")
+    return grad_levels
+
+
+@_on_device
+def corr_pyramid_backward(grad_levels, norm):
+    """mpf_corr_pyramid_backward: folds a gradient pyramid into the gradient of the raw product, in place in grad_levels[0], which it returns
+    ([B*H*W, H, W]); the other levels are only read.  Asynchronous on the current stream."""
+    lib = _lib.load()
+    a, grad_levels = _corr_volume_args(grad_levels, "corr_pyramid_backward", norm=norm)
+    _lib.check(lib.mpf_corr_pyramid_backward(ctypes.byref(a), _stream()), "mpf_corr_pyramid_backward")
+    return grad_levels[0]
 
 
 def _up_tensor(t, name, shape, who):

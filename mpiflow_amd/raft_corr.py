@@ -1,4 +1,5 @@
-"""RAFT's on-demand correlation lookup on the GPU: a drop-in for RAFT/core/corr.py's AlternateCorrBlock and for the `alt_cuda_corr`
+"""RAFT's two correlation blocks on the GPU.  CorrBlock (the class of that name below): the all-pairs default of RAFT/core/corr.py, its
+per-iteration work fused in HIP.  The rest of this module is RAFT's on-demand correlation lookup: a drop-in for RAFT/core/corr.py's AlternateCorrBlock and for the `alt_cuda_corr`
 extension it calls (RAFT/alt_cuda_corr), which has no ROCm build.
 
 Two ways in:
@@ -85,6 +86,108 @@ class AlternateCorrBlock:
 
     def __call__(self, coords):
         return _CorrLookup.apply(coords, self.radius, self.fmap1_nhwc, *self.f2_levels_nhwc)
+
+
+class _GradPyramid:
+    """What the autograd nodes of one CorrBlock share: the gradient pyramid every lookup's backward adds into.  Allocated and zeroed at the
+    first backward call of a lookup, handed over (and forgotten) when the pyramid's own backward folds it."""
+
+    def __init__(self):
+        self.levels = None
+
+
+class _CorrPyramid(torch.autograd.Function):
+    """(fmap1, fmap2) -> the levels of the all-pairs pyramid.  Its cotangents do not arrive as arguments (the lookups return None for the
+    levels) but in `shared`, complete when autograd runs this node: a node runs after every node that depends on it has run."""
+
+    @staticmethod
+    def forward(ctx, shared, num_levels, fmap1, fmap2):
+        B, C, H, W = fmap1.shape
+        ctx.shared, ctx.norm = shared, float(torch.sqrt(torch.tensor(C).float()))          # RAFT divides by the fp32 sqrt(C)
+        ctx.save_for_backward(fmap1, fmap2)
+        ctx.set_materialize_grads(False)
+        raw = torch.matmul(fmap1.view(B, C, H * W).transpose(1, 2), fmap2.view(B, C, H * W))
+        levels = ops.corr_pyramid(raw.view(B * H * W, H, W), num_levels, ctx.norm)        # level 0 is raw itself, scaled in place
+        return tuple(t.unsqueeze(1) for t in levels)
+
+    @staticmethod
+    def backward(ctx, *unused):
+        grad, ctx.shared.levels = ctx.shared.levels, None
+        if grad is None:                                         # no lookup of this block reached the loss
+            return None, None, None, None
+        fmap1, fmap2 = ctx.saved_tensors
+        B, C, H, W = fmap1.shape
+        g = ops.corr_pyramid_backward(grad, ctx.norm).view(B, H * W, H * W)
+        del grad
+        g1 = torch.matmul(fmap2.view(B, C, H * W), g.transpose(1, 2)).view(B, C, H, W) if ctx.needs_input_grad[2] else None
+        g2 = torch.matmul(fmap1.view(B, C, H * W), g).view(B, C, H, W) if ctx.needs_input_grad[3] else None
+        return None, None, g1, g2
+
+
+class _CorrVolumeLookup(torch.autograd.Function):
+    """out = corr_volume_lookup(levels, coords).  Its backward adds into the block's shared gradient pyramid and returns None for every input."""
+
+    @staticmethod
+    def forward(ctx, shared, radius, coords, *levels):
+        ctx.shared, ctx.radius, ctx.shapes = shared, radius, [t.shape for t in levels]
+        ctx.save_for_backward(coords)
+        return ops.corr_volume_lookup([t.squeeze(1) for t in levels], coords, radius)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        coords, = ctx.saved_tensors
+        if ctx.shared.levels is None:
+            ctx.shared.levels = [torch.zeros((s[0], s[2], s[3]), dtype=torch.float32, device=coords.device) for s in ctx.shapes]
+        ops.corr_volume_lookup_backward(ctx.shared.levels, coords, grad_out.contiguous(), ctx.radius)
+        return (None,) * (3 + len(ctx.shapes))
+
+
+class CorrBlock:
+    """RAFT/core/corr.py's CorrBlock: CorrBlock(fmap1, fmap2, num_levels=4, radius=4)(coords) -> [B, L*(2r+1)^2, H, W], the reference's values
+    and channel order (the first window index moves x).  fmap1, fmap2 [B,C,H,W] float32, contiguous, on the GPU, H and W at least
+    2^num_levels; coords [B,2,H,W] (x, y), any values: NaN, +-inf and far-out ones give exactly 0.  Usable as `corr_fn` in
+    RAFT/core/raft.py:104-107 unchanged.  `corr_pyramid` is upstream's list of [B*H*W, 1, H_l, W_l] tensors.
+
+    Construction is one torch.matmul and one launch (mpf_corr_pyramid: 1/sqrt(C) applied to the product in place, the other levels written in
+    the same pass); a lookup is one launch for all levels (mpf_corr_volume_lookup).  Differentiable with respect to fmap1 and fmap2; coords get
+    no gradient (None), as in AlternateCorrBlock.  The backward pass of every lookup ADDS into one gradient pyramid owned by the block
+    (mpf_corr_volume_lookup_backward: no atomics, nothing zero-filled per lookup), allocated and zeroed at the first such call; the node that
+    produced the pyramid runs last, folds it (mpf_corr_pyramid_backward), does the two GEMMs and releases it.  Every kernel result is
+    bit-identical from run to run.  Under torch.no_grad(), or when neither map requires a gradient, none of this is allocated.  A lookup's
+    backward needs the coordinates and the levels' shapes, not the pyramid: a block dropped before backward() (RAFT.forward's on return) frees it.
+
+    Not supported: torch.autograd.grad with respect to `corr_pyramid` itself (its levels receive no cotangent: the gradient travels in the
+    shared buffer), double backward, and backward passes of two lookups of ONE block running at the same time on different streams (they add
+    into the same buffer).  A backward pass that reaches some lookups but not fmap1 / fmap2 leaves the buffer allocated until the block dies."""
+
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
+        for t, name in ((fmap1, "fmap1"), (fmap2, "fmap2")):
+            if not isinstance(t, torch.Tensor):
+                raise MpiFlowHipError("CorrBlock: %s must be a tensor (got %s)" % (name, type(t).__name__))
+            if t.dtype != torch.float32:
+                raise MpiFlowHipError("CorrBlock: %s must be float32 (got %s)" % (name, t.dtype))
+            if t.dim() != 4 or not t.is_contiguous():
+                raise MpiFlowHipError("CorrBlock: %s must be a contiguous [B,C,H,W] tensor (got shape %s, contiguous %s)"
+                                      % (name, tuple(t.shape), t.is_contiguous()))
+        if fmap1.shape != fmap2.shape or fmap1.device != fmap2.device:
+            raise MpiFlowHipError("CorrBlock: fmap1 %s on %s and fmap2 %s on %s must agree"
+                                  % (tuple(fmap1.shape), fmap1.device, tuple(fmap2.shape), fmap2.device))
+        B, C, H, W = fmap1.shape
+        if not 1 <= int(num_levels) <= CORR_MAX_LEVELS:
+            raise MpiFlowHipError("CorrBlock: num_levels must be 1..%d (got %s)" % (CORR_MAX_LEVELS, num_levels))
+        if not 1 <= int(radius) <= 8:
+            raise MpiFlowHipError("CorrBlock: radius must be 1..8 (got %s)" % (radius,))
+        if min(H, W) < 2 ** int(num_levels):
+            raise MpiFlowHipError("CorrBlock: H, W = %d, %d must be at least 2^num_levels = %d (every level at least 2 x 2)"
+                                  % (H, W, 2 ** int(num_levels)))
+        if not fmap1.is_cuda:
+            raise MpiFlowHipError("CorrBlock: fmap1 and fmap2 must be on the GPU (got %s); mpiflow_amd has no CPU path" % fmap1.device)
+        self.num_levels, self.radius = int(num_levels), int(radius)
+        self._shared = _GradPyramid()
+        self.corr_pyramid = list(_CorrPyramid.apply(self._shared, self.num_levels, fmap1, fmap2))
+
+    def __call__(self, coords):
+        return _CorrVolumeLookup.apply(self._shared, self.radius, coords, *self.corr_pyramid)
 
 
 def _ext_coords(coords, fmap1):

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Time RAFT's correlation lookup two ways on one GPU, in one process, alternating: (a) the all-pairs form in torch (CorrBlock restated: the
-(HW)^2 volume by matmul, its avg_pool2d pyramid once, then 12 grid_sample lookups) and (b) mpiflow_amd.raft_corr.AlternateCorrBlock (the
-channel-last maps once, then 12 launches of mpf_corr_lookup), forward only and with the backward pass of all 12 lookups; plus the peak
-memory of each, and the time of ONE forward lookup of the shipped kernel beside the plain one-thread-per-entry kernel it grew from.
+"""Time RAFT's correlation lookup three ways on one GPU, in one process, alternating: (a) the all-pairs form in torch (CorrBlock restated: the
+(HW)^2 volume by matmul, its avg_pool2d pyramid once, then 12 grid_sample lookups), (b) mpiflow_amd.raft_corr.AlternateCorrBlock (the
+channel-last maps once, then 12 launches of mpf_corr_lookup) and (c) mpiflow_amd.raft_corr.CorrBlock (the all-pairs form with its pyramid,
+lookups and gradients in HIP), forward only and with the backward pass of all 12 lookups; plus the peak memory of each, the time of ONE
+forward lookup of the on-demand kernel beside the plain one-thread-per-entry kernel it grew from, and the four ops of (c) alone.
 
     python tools/bench_corr.py [--reps 10] [--warmup 2] [--lookups 12] [--shapes 8x36x120,8x48x160,2x128x192] [--channels 256] [--json PATH]
 
@@ -96,7 +97,8 @@ def main():
         flow = torch.stack([3.0 * torch.sin(ys / 9.0) + 2.0, 2.0 * torch.cos(xs / 11.0)])[None]
         coords = [(grid + flow * (k + 1) / a.lookups + 0.25 * torch.randn(B, 2, H, W, generator=gen)).to(dev).contiguous() for k in range(a.lookups)]
         row = dict(B=B, C=C, H=H, W=W, lookups=a.lookups)
-        forms = (("allpairs", AllPairs), ("ondemand", lambda x, y: raft_corr.AlternateCorrBlock(x, y, num_levels=L, radius=R)))
+        forms = (("allpairs", AllPairs), ("ondemand", lambda x, y: raft_corr.AlternateCorrBlock(x, y, num_levels=L, radius=R)),
+                 ("volume", lambda x, y: raft_corr.CorrBlock(x, y, num_levels=L, radius=R)))
         for backward in (False, True):
             ts = {n: [] for n, _ in forms}
             for k in range(a.warmup + a.reps):                       # alternating: one step of each form per round
@@ -128,6 +130,22 @@ def main():
         flop = 2.0 * B * H * W * L * 100 * C                           # the (rd+1)^2 grid dot products of every pixel and level
         row["lookup_TFLOPs"] = flop / (row["lookup_kernel_ms"] * 1e-3) / 1e12
         row["lookup_grid_bytes_MB"] = B * H * W * L * 100 * C * 4 / 1e6
+        del blk
+        # the four ops of CorrBlock alone, on buffers of their own.  The pyramid op rescales its level 0 at every call (values shrink, time does
+        # not) and allocates levels 1.. each time (caching-allocator hits): it is the op, not the bare kernel; the other three allocate nothing
+        norm = float(torch.sqrt(torch.tensor(C).float()))
+        raw = torch.matmul(f1.view(B, C, H * W).transpose(1, 2), f2.view(B, C, H * W)).view(B * H * W, H, W)
+        levels = ops.corr_pyramid(raw, L, norm)
+        grads = [torch.zeros_like(t) for t in levels]
+        kernels = (("volume_pyramid_kernel_ms", lambda: ops.corr_pyramid(raw, L, norm)),
+                   ("volume_lookup_kernel_ms", lambda: ops.corr_volume_lookup(levels, coords[-1], R, out=out)),
+                   ("volume_lookup_backward_kernel_ms", lambda: ops.corr_volume_lookup_backward(grads, coords[-1], g, R)),
+                   ("volume_fold_kernel_ms", lambda: ops.corr_pyramid_backward(grads, norm)))
+        for name, fn in kernels:
+            row[name] = statistics.median(timed(fn, a.reps, a.warmup))
+        row["volume_pyramid_MB"] = sum(t.numel() for t in levels) * 4 / 1e6
+        row["volume_lookup_bytes_MB"] = B * H * W * L * (100 + 81) * 4 / 1e6       # the patches read + the outputs written
+        del raw, levels, grads
         rows.append(row)
         print(json.dumps(row), flush=True)
     print("\n| B x H x W | all-pairs fwd ms | on-demand fwd ms | all-pairs fwd+bwd ms | on-demand fwd+bwd ms | all-pairs peak MB | on-demand peak MB | "
@@ -137,6 +155,13 @@ def main():
         print("| %d x %d x %d | %.2f | %.2f | %.2f | %.2f | %.0f | %.0f | %.3f | %.3f | %.3f | %.1f |" % (
             r["B"], r["H"], r["W"], r["allpairs_fwd_ms"], r["ondemand_fwd_ms"], r["allpairs_fwd_bwd_ms"], r["ondemand_fwd_bwd_ms"],
             r["allpairs_peak_MB"], r["ondemand_peak_MB"], r["lookup_kernel_ms"], r["lookup_plain_kernel_ms"], r["lookup_backward_kernel_ms"], r["lookup_TFLOPs"]))
+    print("\n| B x H x W | CorrBlock fwd ms | CorrBlock fwd+bwd ms | CorrBlock peak MB | pyramid MB | pyramid op ms | lookup kernel ms | "
+          "lookup backward kernel ms | fold kernel ms |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    for r in rows:
+        print("| %d x %d x %d | %.2f | %.2f | %.0f | %.0f | %.3f | %.3f | %.3f | %.3f |" % (
+            r["B"], r["H"], r["W"], r["volume_fwd_ms"], r["volume_fwd_bwd_ms"], r["volume_peak_MB"], r["volume_pyramid_MB"], r["volume_pyramid_kernel_ms"],
+            r["volume_lookup_kernel_ms"], r["volume_lookup_backward_kernel_ms"], r["volume_fold_kernel_ms"]))
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
