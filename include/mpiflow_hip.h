@@ -37,7 +37,9 @@ extern "C" {
                              round 5 (501): + the parity-grade producer engine mpf_pconv, mpf_pfmn_input, mpf_pencoder_input, mpf_pbilinear2x, mpf_pper_plane,
                              mpf_pplane_masks, mpf_pmaxpool3x3s2; MpfMergeArgs + obj_mask_stride, mpf_merge_ex, mpf_src_flow_hard;
                              (503): MpfConvArgs + bprime_table, pw (planes per workgroup of the few-block layers);
-                             round 6 (601): + loader 6 (MPF_CONV_LD_NEAREST_PHASE), mpf_tune("fwarp_gate"), mpf_forward_warp_workspace + 256 bytes */
+                             round 6 (601): + loader 6 (MPF_CONV_LD_NEAREST_PHASE), mpf_tune("fwarp_gate"), mpf_forward_warp_workspace + 256 bytes;
+                             the RAFT entry points added since (mpf_corr_*, mpf_upsample_*, mpf_flow_loss_term*, and now mpf_gru_reset, mpf_gru_update and
+                             their _backward calls with MpfGruTerm / MpfGruArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
 
 /* d_params layout (floats):
  *   [0..8]   K_src^-1 (3x3 row-major)            [9..20]  G_tgt_src rows 0..2 (3x4 row-major: R | t)
@@ -518,6 +520,42 @@ int mpf_upsample_flow(const MpfUpsampleArgs *a, void *stream);
 int mpf_upsample_flow_backward(const MpfUpsampleArgs *a, void *stream);
 int mpf_flow_loss_term(const MpfUpsampleArgs *a, void *stream);
 int mpf_flow_loss_term_backward(const MpfUpsampleArgs *a, void *stream);
+
+/* The pointwise work of RAFT's convolutional GRU (ConvGRU / SepConvGRU, RAFT/core/update.py:16-60) between its gate convolutions, fused.
+ * All tensors f32, NCHW, contiguous.  A pre-activation is the sum of up to MPF_GRU_MAX_TERMS terms; a term is the channel slice
+ * [offset, offset + C) of a tensor [B,channels,H,W], read in place; p = NULL: the term is absent (one of the counted terms must be present).
+ * Gradients of pre-activations are written the same way, each to up to two slices (index 0 required, index 1 optional).
+ *   mpf_gru_reset            out = rh = sigmoid(sum r) * h                                                           [B,C,H,W]
+ *   mpf_gru_update           z = sigmoid(sum z), q = tanh(sum q);  out = h' = (1 - z) * h + z * q                    [B,C,H,W]
+ *   mpf_gru_update_backward  g = grad h'; recomputes z, q;  dz <- g (q - h) z (1 - z),  dq <- g z (1 - q^2),  dh = g (1 - z)   (dh WRITTEN)
+ *   mpf_gru_reset_backward   g = grad rh; recomputes r;     dr <- g h r (1 - r);  dh = g r, or dh += g r with accumulate != 0
+ * 16-byte accesses when H*W % 4 == 0 and every pointer (slice offsets applied) is 16-byte aligned, 4-byte ones otherwise: any B, C, H, W >= 1
+ * with every tensor below 2^31 elements.  No atomics: bit-identical from run to run.  Tensor VALUES are unrestricted: NaN and inf propagate as
+ * they do in torch and no value changes an address.  Outputs must not overlap inputs (dh with accumulate excepted).  Validated before anything
+ * is launched (MPF_ERR_BAD_ARGUMENT): NULL required pointers, non-positive sizes, offset + C > channels, a term count outside 1..3. */
+#define MPF_GRU_MAX_TERMS 3
+typedef struct MpfGruTerm {
+    float *p;                    /* the tensor's first element, NOT the slice's; read only where the term is an input */
+    int channels;                /* of that tensor */
+    int offset;                  /* first channel of the slice */
+} MpfGruTerm;
+typedef struct MpfGruArgs {
+    MpfGruTerm z[MPF_GRU_MAX_TERMS];     /* update calls */
+    MpfGruTerm r[MPF_GRU_MAX_TERMS];     /* reset calls */
+    MpfGruTerm q[MPF_GRU_MAX_TERMS];     /* update calls */
+    MpfGruTerm dz[2], dr[2], dq[2];      /* backward calls: written */
+    const float *h;              /* [B,C,H,W] */
+    const float *g;              /* backward calls: the cotangent [B,C,H,W] */
+    float *out;                  /* forward calls: written */
+    float *dh;                   /* backward calls: [B,C,H,W] */
+    int nz, nr, nq;              /* terms counted in z, r, q: 1..MPF_GRU_MAX_TERMS where the call uses them */
+    int accumulate;              /* mpf_gru_reset_backward: add into dh */
+    int B, C, H, W;
+} MpfGruArgs;
+int mpf_gru_reset(const MpfGruArgs *a, void *stream);
+int mpf_gru_update(const MpfGruArgs *a, void *stream);
+int mpf_gru_update_backward(const MpfGruArgs *a, void *stream);
+int mpf_gru_reset_backward(const MpfGruArgs *a, void *stream);
 
 /* [3,H,W] float RGB -> [H,W,3] u8 BGR, clip(rint(x*255))  (utils/utils.py:174-177) */
 int mpf_to_u8_bgr(const float *d_img, int H, int W, uint8_t *d_out, void *stream);

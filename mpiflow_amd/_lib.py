@@ -126,6 +126,21 @@ class MpfUpsampleArgs(ctypes.Structure):
                 ("N", c_i), ("H", c_i), ("W", c_i), ("max_flow", c_f)]
 
 
+GRU_MAX_TERMS = 3       # MPF_GRU_MAX_TERMS
+
+
+class MpfGruTerm(ctypes.Structure):
+    """struct MpfGruTerm of include/mpiflow_hip.h: the channel slice [offset, offset + C) of a [B,channels,H,W] tensor (device pointer)."""
+    _fields_ = [("p", c_p), ("channels", c_i), ("offset", c_i)]
+
+
+class MpfGruArgs(ctypes.Structure):
+    """struct MpfGruArgs of include/mpiflow_hip.h: the pointwise work of RAFT's convolutional GRU, forward and gradient (device pointers)."""
+    _fields_ = [("z", MpfGruTerm * GRU_MAX_TERMS), ("r", MpfGruTerm * GRU_MAX_TERMS), ("q", MpfGruTerm * GRU_MAX_TERMS),
+                ("dz", MpfGruTerm * 2), ("dr", MpfGruTerm * 2), ("dq", MpfGruTerm * 2), ("h", c_p), ("g", c_p), ("out", c_p), ("dh", c_p),
+                ("nz", c_i), ("nr", c_i), ("nq", c_i), ("accumulate", c_i), ("B", c_i), ("C", c_i), ("H", c_i), ("W", c_i)]
+
+
 MAX_VIEWS = 16          # MPF_MAX_VIEWS
 SUPPORT_CELL_W, SUPPORT_CELL_H = 32, 8      # MPF_SUPPORT_CELL_W / _H
 
@@ -179,6 +194,10 @@ SIGNATURES = {
     "mpf_upsample_flow_backward": (c_i, [ctypes.POINTER(MpfUpsampleArgs), c_p]),
     "mpf_flow_loss_term": (c_i, [ctypes.POINTER(MpfUpsampleArgs), c_p]),
     "mpf_flow_loss_term_backward": (c_i, [ctypes.POINTER(MpfUpsampleArgs), c_p]),
+    "mpf_gru_reset": (c_i, [ctypes.POINTER(MpfGruArgs), c_p]),
+    "mpf_gru_update": (c_i, [ctypes.POINTER(MpfGruArgs), c_p]),
+    "mpf_gru_update_backward": (c_i, [ctypes.POINTER(MpfGruArgs), c_p]),
+    "mpf_gru_reset_backward": (c_i, [ctypes.POINTER(MpfGruArgs), c_p]),
     "mpf_src_xyz": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
     "mpf_transform_xyz": (c_i, [c_p, c_p, c_i, c_i64, c_p, c_p]),
     "mpf_homography_sample": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),

@@ -1015,6 +1015,111 @@ def flow_loss_term_backward(flow, mask, flow_gt, valid, g, max_flow=400):
     return gf, gm
 
 
+def _gru_tensor(t, name, who, shape=None, on_gpu=True):
+    """The GRU kernels take their tensors as they are: no silent copy, cast or move.  on_gpu=False leaves the device to the caller, who checks
+    it after every tensor's own checks so that a wrong dtype or shape is named as such on any device."""
+    if not isinstance(t, torch.Tensor):
+        raise _lib.MpiFlowHipError("%s: %s must be a torch.Tensor (got %s)" % (who, name, type(t).__name__))
+    if t.dtype != _f32:
+        hint = "; call .float() on it (a half-precision kernel does not exist)" if t.dtype in (torch.float16, torch.bfloat16) else ""
+        raise _lib.MpiFlowHipError("%s: %s must be float32 (got %s)%s" % (who, name, t.dtype, hint))
+    if t.dim() != 4 or (shape is not None and any(s is not None and s != d for s, d in zip(shape, t.shape))):
+        raise _lib.MpiFlowHipError("%s: %s must be %s (got shape %s)" % (who, name, list(shape) if shape else "[B,C,H,W]", tuple(t.shape)))
+    if not t.is_contiguous():
+        raise _lib.MpiFlowHipError("%s: %s must be contiguous" % (who, name))
+    if on_gpu and not t.is_cuda:
+        raise _lib.MpiFlowHipError("%s: %s must live on the GPU (got %s); mpiflow_amd has no CPU path" % (who, name, t.device))
+    return t
+
+
+def _gru_slices(dst, terms, name, who, h, limit):
+    """terms: (tensor [B,channels,H,W], channel offset) pairs or None (absent) -> fills the MpfGruTerm array `dst`, returns the count"""
+    terms = list(terms)
+    if not 1 <= len(terms) <= limit:
+        raise _lib.MpiFlowHipError("%s: %s takes 1..%d slices (got %d)" % (who, name, limit, len(terms)))
+    B, C, H, W = h.shape
+    for k, term in enumerate(terms):
+        if term is None:
+            continue
+        t, off = term
+        t = _gru_tensor(t, "%s[%d]" % (name, k), who, (B, None, H, W))
+        if t.device != h.device:
+            raise _lib.MpiFlowHipError("%s: %s[%d] on %s must share h's device %s" % (who, name, k, t.device, h.device))
+        if off < 0 or off + C > t.shape[1]:
+            raise _lib.MpiFlowHipError("%s: %s[%d]: channels [%d, %d) are not inside its %d channels" % (who, name, k, off, off + C, t.shape[1]))
+        dst[k].p, dst[k].channels, dst[k].offset = t.data_ptr(), t.shape[1], int(off)
+    return len(terms)
+
+
+def _gru_args(h, who):
+    h = _gru_tensor(h, "h", who)
+    a = _lib.MpfGruArgs()
+    a.h = h.data_ptr()
+    a.B, a.C, a.H, a.W = h.shape
+    return a
+
+
+@_on_device
+def gru_reset(h, r_terms):
+    """mpf_gru_reset: rh = sigmoid(sum of r_terms) * h.  h [B,C,H,W]; a term is (tensor [B,channels,H,W], channel offset) - the slice
+    [offset, offset + C) read in place - or None.  float32, contiguous, on the GPU, or MpiFlowHipError.  Asynchronous on the current stream."""
+    lib = _lib.load()
+    a = _gru_args(h, "gru_reset")
+    a.nr = _gru_slices(a.r, r_terms, "r_terms", "gru_reset", h, _lib.GRU_MAX_TERMS)
+    out = torch.empty_like(h)
+    a.out = out.data_ptr()
+    _lib.check(lib.mpf_gru_reset(ctypes.byref(a), _stream()), "mpf_gru_reset")
+    return out
+
+
+@_on_device
+def gru_update(h, z_terms, q_terms):
+    """mpf_gru_update: h' = (1 - z) * h + z * q with z = sigmoid(sum of z_terms), q = tanh(sum of q_terms); terms as in gru_reset."""
+    lib = _lib.load()
+    a = _gru_args(h, "gru_update")
+    a.nz = _gru_slices(a.z, z_terms, "z_terms", "gru_update", h, _lib.GRU_MAX_TERMS)
+    a.nq = _gru_slices(a.q, q_terms, "q_terms", "gru_update", h, _lib.GRU_MAX_TERMS)
+    out = torch.empty_like(h)
+    a.out = out.data_ptr()
+    _lib.check(lib.mpf_gru_update(ctypes.byref(a), _stream()), "mpf_gru_update")
+    return out
+
+
+@_on_device
+def gru_update_backward(grad_out, h, z_terms, q_terms, dz, dq):
+    """mpf_gru_update_backward: the cotangent grad_out of gru_update's h' -> d h = grad_out * (1 - z), returned; d pre_z and d pre_q are WRITTEN
+    into the slices dz and dq: one or two (tensor, channel offset) destinations each.  z and q are recomputed from the terms."""
+    lib = _lib.load()
+    who = "gru_update_backward"
+    a = _gru_args(h, who)
+    g = _gru_tensor(grad_out, "grad_out", who, tuple(h.shape))
+    a.nz = _gru_slices(a.z, z_terms, "z_terms", who, h, _lib.GRU_MAX_TERMS)
+    a.nq = _gru_slices(a.q, q_terms, "q_terms", who, h, _lib.GRU_MAX_TERMS)
+    _gru_slices(a.dz, dz, "dz", who, h, 2)
+    _gru_slices(a.dq, dq, "dq", who, h, 2)
+    dh = torch.empty_like(h)
+    a.g, a.dh = g.data_ptr(), dh.data_ptr()
+    _lib.check(lib.mpf_gru_update_backward(ctypes.byref(a), _stream()), "mpf_gru_update_backward")
+    return dh
+
+
+@_on_device
+def gru_reset_backward(grad_out, h, r_terms, dr, dh=None):
+    """mpf_gru_reset_backward: the cotangent grad_out of gru_reset's rh -> d pre_r WRITTEN into the slices dr (one or two destinations);
+    d h = grad_out * r is ADDED into `dh` when one is given, otherwise written to a fresh tensor.  Returns dh."""
+    lib = _lib.load()
+    who = "gru_reset_backward"
+    a = _gru_args(h, who)
+    g = _gru_tensor(grad_out, "grad_out", who, tuple(h.shape))
+    a.nr = _gru_slices(a.r, r_terms, "r_terms", who, h, _lib.GRU_MAX_TERMS)
+    _gru_slices(a.dr, dr, "dr", who, h, 2)
+    a.accumulate = int(dh is not None)
+    dh = torch.empty_like(h) if dh is None else _gru_tensor(dh, "dh", who, tuple(h.shape))
+    a.g, a.dh = g.data_ptr(), dh.data_ptr()
+    _lib.check(lib.mpf_gru_reset_backward(ctypes.byref(a), _stream()), "mpf_gru_reset_backward")
+    return dh
+
+
 @_on_device
 def to_u8_bgr(img_3HW):
     lib = _lib.load()
