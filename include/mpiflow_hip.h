@@ -39,7 +39,8 @@ extern "C" {
                              (503): MpfConvArgs + bprime_table, pw (planes per workgroup of the few-block layers);
                              round 6 (601): + loader 6 (MPF_CONV_LD_NEAREST_PHASE), mpf_tune("fwarp_gate"), mpf_forward_warp_workspace + 256 bytes;
                              the RAFT entry points added since (mpf_corr_*, mpf_upsample_*, mpf_flow_loss_term*, and now mpf_gru_reset, mpf_gru_update and
-                             their _backward calls with MpfGruTerm / MpfGruArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
+                             their _backward calls with MpfGruTerm / MpfGruArgs, and now mpf_norm_stats, mpf_norm_act, mpf_norm_act_backward_reduce and
+                             mpf_norm_act_backward with MpfNormTerm / MpfNormArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
 
 /* d_params layout (floats):
  *   [0..8]   K_src^-1 (3x3 row-major)            [9..20]  G_tgt_src rows 0..2 (3x4 row-major: R | t)
@@ -556,6 +557,72 @@ int mpf_gru_reset(const MpfGruArgs *a, void *stream);
 int mpf_gru_update(const MpfGruArgs *a, void *stream);
 int mpf_gru_update_backward(const MpfGruArgs *a, void *stream);
 int mpf_gru_reset_backward(const MpfGruArgs *a, void *stream);
+
+/* The memory-bound chain between the convolutions of RAFT's encoders (ResidualBlock / BottleneckBlock / BasicEncoder / SmallEncoder,
+ * RAFT/core/extractor.py): normalise, ReLU, add the shortcut, ReLU - forward and gradient, fused.  All tensors f32, NCHW, contiguous; the per-chunk partial sums are fp64
+ * (a few numbers per plane), so that splitting a plane into chunks does not add an fp32 rounding per chunk to the statistics.
+ * A TERM is an activation x [N,C,H,W] with a norm mode; a statistic SET is what one mean / variance is taken over:
+ *   MPF_NORM_NONE         identity
+ *   MPF_NORM_INSTANCE     sets (n, c) over H*W, biased variance                         N*C sets
+ *   MPF_NORM_BATCH_TRAIN  sets c over N*H*W                                             C sets
+ *   MPF_NORM_BATCH_EVAL   running_mean / running_var [C], no reduction at all
+ *   MPF_NORM_GROUP        sets (n, g) over the C/groups channels of group g             N*groups sets
+ * normalised value = (x - mean) * rstd * weight[c] + bias[c], rstd = 1 / sqrt(var + 1e-5); weight and bias are optional (NULL: 1 and 0).
+ *   mpf_norm_stats    per present term with a statistics mode: partials[N,C,chunks,2] <- (mean, centred sum of squares M2) of chunk k of
+ *                     plane (n, c): the elements [k*L, min((k+1)*L, H*W)), L = ceil(H*W / chunks) rounded up to a multiple of 4 (a chunk may
+ *                     be empty: (0, 0)).  Sums of (x - x[first]) and its square in fp64: no E[x^2] - E[x]^2 cancellation.
+ *   mpf_norm_act      out = relu(norm(y.x)); with a residual - `res`, a plain tensor, or the term `r`, normalised WITHOUT a ReLU - out =
+ *                     relu(residual + relu(norm(y.x))).  Every workgroup merges the partials of its set with Chan's formula in a fixed order
+ *                     (fp64); mean[set], rstd[set] and, where non-NULL, var[set] (biased) are written once.
+ *   mpf_norm_act_backward_reduce   g = grad out; recomputes both ReLU masks from the same inputs and mean / rstd;
+ *                     grad_partials[N,C,chunks,2] <- (sum dy, sum dy * xhat) per chunk for every normalised term that has the buffer.
+ *   mpf_norm_act_backward          merges those in a fixed order; dx <- rstd * (dy * weight - mean(dy weight) - xhat * mean(dy weight xhat)) per
+ *                     set (BATCH_EVAL: dy * weight * rstd, NONE: dy; neither reads grad_partials for dx); dweight[c] <- sum dy * xhat, dbias[c]
+ *                     <- sum dy where non-NULL (these need grad_partials in every normalised mode); dres <- the shortcut's gradient, or dres +=
+ *                     with accumulate != 0.
+ * relu(v) = v < 0 ? 0 : v and its gradient passes where !(v <= 0): NaN stays where torch keeps it.  16-byte accesses when H*W % 4 == 0 and
+ * every tensor pointer is 16-byte aligned, 4-byte ones otherwise; the chunk layout does not depend on that.  No atomics: bit-identical from
+ * call to call for equal arguments (chunks included).  Outputs must not overlap inputs (dres with accumulate excepted).  Validated before
+ * anything is launched (MPF_ERR_BAD_ARGUMENT): NULL required pointers, a mode outside 0..4, groups < 1 or C % groups != 0, chunks outside
+ * 1..MPF_NORM_MAX_CHUNKS, non-positive sizes, N*C*max(H*W, chunks) >= 2^31, both `res` and `r`. */
+#define MPF_NORM_NONE 0
+#define MPF_NORM_INSTANCE 1
+#define MPF_NORM_BATCH_TRAIN 2
+#define MPF_NORM_BATCH_EVAL 3
+#define MPF_NORM_GROUP 4
+#define MPF_NORM_MAX_CHUNKS 1024
+typedef struct MpfNormTerm {
+    const float *x;              /* [N,C,H,W]; NULL: the term is absent (r only) */
+    const float *weight;         /* [C] or NULL */
+    const float *bias;           /* [C] or NULL */
+    const float *running_mean;   /* [C], BATCH_EVAL */
+    const float *running_var;    /* [C], BATCH_EVAL */
+    double *partials;            /* [N,C,chunks,2] fp64: written by mpf_norm_stats, read by mpf_norm_act */
+    float *mean;                 /* [sets]: written by mpf_norm_act, read by the backward calls */
+    float *rstd;                 /* [sets]: likewise */
+    float *var;                  /* [sets] or NULL: written by mpf_norm_act (biased variance, for running statistics) */
+    double *grad_partials;       /* [N,C,chunks,2] fp64: written by mpf_norm_act_backward_reduce, read by mpf_norm_act_backward */
+    float *dx;                   /* [N,C,H,W]: written by mpf_norm_act_backward */
+    float *dweight;              /* [C] or NULL */
+    float *dbias;                /* [C] or NULL */
+    int mode;                    /* MPF_NORM_* */
+    int groups;                  /* GROUP: divides C; otherwise ignored */
+} MpfNormTerm;
+typedef struct MpfNormArgs {
+    MpfNormTerm y;               /* the main term */
+    MpfNormTerm r;               /* the residual as a normalised term (r.x != NULL), e.g. norm3(conv1x1(x)) of a strided block */
+    const float *res;            /* or the residual as a plain tensor [N,C,H,W] (identity shortcut); NULL with r.x NULL: no residual */
+    float *out;                  /* mpf_norm_act: written */
+    const float *g;              /* backward calls: the cotangent of out */
+    float *dres;                 /* mpf_norm_act_backward with `res`: written, or added to with accumulate */
+    int accumulate;
+    int chunks;                  /* 1..MPF_NORM_MAX_CHUNKS; the same number in all four calls of one forward / backward */
+    int N, C, H, W;
+} MpfNormArgs;
+int mpf_norm_stats(const MpfNormArgs *a, void *stream);
+int mpf_norm_act(const MpfNormArgs *a, void *stream);
+int mpf_norm_act_backward_reduce(const MpfNormArgs *a, void *stream);
+int mpf_norm_act_backward(const MpfNormArgs *a, void *stream);
 
 /* [3,H,W] float RGB -> [H,W,3] u8 BGR, clip(rint(x*255))  (utils/utils.py:174-177) */
 int mpf_to_u8_bgr(const float *d_img, int H, int W, uint8_t *d_out, void *stream);

@@ -141,6 +141,22 @@ class MpfGruArgs(ctypes.Structure):
                 ("nz", c_i), ("nr", c_i), ("nq", c_i), ("accumulate", c_i), ("B", c_i), ("C", c_i), ("H", c_i), ("W", c_i)]
 
 
+NORM_NONE, NORM_INSTANCE, NORM_BATCH_TRAIN, NORM_BATCH_EVAL, NORM_GROUP = range(5)      # MPF_NORM_*
+NORM_MAX_CHUNKS = 1024  # MPF_NORM_MAX_CHUNKS
+
+
+class MpfNormTerm(ctypes.Structure):
+    """struct MpfNormTerm of include/mpiflow_hip.h: one activation with its norm mode, statistics and gradient buffers (device pointers)."""
+    _fields_ = [("x", c_p), ("weight", c_p), ("bias", c_p), ("running_mean", c_p), ("running_var", c_p), ("partials", c_p), ("mean", c_p),
+                ("rstd", c_p), ("var", c_p), ("grad_partials", c_p), ("dx", c_p), ("dweight", c_p), ("dbias", c_p), ("mode", c_i), ("groups", c_i)]
+
+
+class MpfNormArgs(ctypes.Structure):
+    """struct MpfNormArgs of include/mpiflow_hip.h: the norm / ReLU / shortcut / ReLU chain of RAFT's encoders, forward and gradient."""
+    _fields_ = [("y", MpfNormTerm), ("r", MpfNormTerm), ("res", c_p), ("out", c_p), ("g", c_p), ("dres", c_p), ("accumulate", c_i),
+                ("chunks", c_i), ("N", c_i), ("C", c_i), ("H", c_i), ("W", c_i)]
+
+
 MAX_VIEWS = 16          # MPF_MAX_VIEWS
 SUPPORT_CELL_W, SUPPORT_CELL_H = 32, 8      # MPF_SUPPORT_CELL_W / _H
 
@@ -198,6 +214,10 @@ SIGNATURES = {
     "mpf_gru_update": (c_i, [ctypes.POINTER(MpfGruArgs), c_p]),
     "mpf_gru_update_backward": (c_i, [ctypes.POINTER(MpfGruArgs), c_p]),
     "mpf_gru_reset_backward": (c_i, [ctypes.POINTER(MpfGruArgs), c_p]),
+    "mpf_norm_stats": (c_i, [ctypes.POINTER(MpfNormArgs), c_p]),
+    "mpf_norm_act": (c_i, [ctypes.POINTER(MpfNormArgs), c_p]),
+    "mpf_norm_act_backward_reduce": (c_i, [ctypes.POINTER(MpfNormArgs), c_p]),
+    "mpf_norm_act_backward": (c_i, [ctypes.POINTER(MpfNormArgs), c_p]),
     "mpf_src_xyz": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
     "mpf_transform_xyz": (c_i, [c_p, c_p, c_i, c_i64, c_p, c_p]),
     "mpf_homography_sample": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),

@@ -1120,6 +1120,212 @@ def gru_reset_backward(grad_out, h, r_terms, dr, dh=None):
     return dh
 
 
+NORM_MODES = {"none": _lib.NORM_NONE, "instance": _lib.NORM_INSTANCE, "batch_train": _lib.NORM_BATCH_TRAIN, "batch_eval": _lib.NORM_BATCH_EVAL,
+              "group": _lib.NORM_GROUP}
+_NORM_STATS = ("instance", "batch_train", "group")
+
+
+class NormTerm:
+    """One term of the encoders' norm / ReLU chain: a convolution output x [N,C,H,W] with a norm mode ('none', 'instance', 'batch_train',
+    'batch_eval', 'group'), optional weight / bias [C], `groups` for 'group', running_mean / running_var [C] for 'batch_eval'.
+    norm_act fills mean, rstd and var (one entry per statistic set; None for 'none' and 'batch_eval'), which norm_act_backward reads;
+    `partials` may hold what norm_stats returned for x (otherwise norm_act computes it)."""
+
+    def __init__(self, x, mode, weight=None, bias=None, groups=1, running_mean=None, running_var=None, partials=None):
+        self.x, self.mode, self.weight, self.bias, self.groups = x, mode, weight, bias, groups
+        self.running_mean, self.running_var, self.partials = running_mean, running_var, partials
+        self.mean = self.rstd = self.var = None
+
+    def sets(self):
+        N, C = self.x.shape[:2]
+        return {"instance": N * C, "batch_train": C, "group": N * self.groups}.get(self.mode, 0)
+
+
+def norm_default_chunks(planes, hw):
+    """how many workgroups share a plane: enough for about 2048 workgroups in all, none with fewer than 4096 elements, 64 at the most"""
+    return max(1, min(-(-2048 // planes), hw // 4096, 64))
+
+
+def _norm_check(term, name, who, shape=None):
+    """a term's own checks: type, dtype, shape, mode, parameters, a single element per statistic set; the device is left to _norm_args, which
+    checks it after everything else so that a wrong dtype, shape or mode is named as such on any device"""
+    if not isinstance(term, NormTerm):
+        raise _lib.MpiFlowHipError("%s: %s must be an ops.NormTerm (got %s)" % (who, name, type(term).__name__))
+    x = _gru_tensor(term.x, name + ".x", who, shape, on_gpu=False)
+    if term.mode not in NORM_MODES:
+        raise _lib.MpiFlowHipError("%s: %s.mode must be one of %s (got %r)" % (who, name, ", ".join(sorted(NORM_MODES)), term.mode))
+    N, C, H, W = x.shape
+    if term.mode == "group" and (not isinstance(term.groups, int) or term.groups < 1 or C % term.groups):
+        raise _lib.MpiFlowHipError("%s: %s.groups must divide the %d channels (got %r)" % (who, name, C, term.groups))
+    per_set = {"instance": H * W, "batch_train": N * H * W}.get(term.mode)
+    if per_set == 1:
+        raise _lib.MpiFlowHipError("%s: %s: '%s' statistics over a single value per %s (shape %s) have no variance; use a larger input or "
+                                   "put the module in eval mode with running statistics" % (who, name, term.mode, "plane" if term.mode == "instance" else "channel", tuple(x.shape)))
+    vecs = [("weight", term.weight), ("bias", term.bias)]
+    if term.mode == "batch_eval":
+        if term.running_mean is None or term.running_var is None:
+            raise _lib.MpiFlowHipError("%s: %s: 'batch_eval' needs running_mean and running_var" % (who, name))
+        vecs += [("running_mean", term.running_mean), ("running_var", term.running_var)]
+    for vname, v in vecs:
+        if v is None:
+            continue
+        if not isinstance(v, torch.Tensor) or v.dtype != _f32 or tuple(v.shape) != (C,) or not v.is_contiguous() or v.device != x.device:
+            raise _lib.MpiFlowHipError("%s: %s.%s must be a contiguous float32 tensor [%d] on %s" % (who, name, vname, C, x.device))
+    return x
+
+
+def _norm_fill(ct, term):
+    ct.x, ct.mode, ct.groups = term.x.data_ptr(), NORM_MODES[term.mode], int(term.groups)
+    if term.mode != "none":
+        for cname, v in (("weight", term.weight), ("bias", term.bias), ("running_mean", term.running_mean), ("running_var", term.running_var),
+                         ("partials", term.partials), ("mean", term.mean), ("rstd", term.rstd), ("var", term.var)):
+            setattr(ct, cname, None if v is None else v.data_ptr())
+
+
+def _norm_args(term, residual, who, chunks):
+    """(MpfNormArgs, y, residual term or None, residual tensor or None): everything checked, nothing allocated"""
+    x = _norm_check(term, "term", who)
+    N, C, H, W = x.shape
+    a = _lib.MpfNormArgs()
+    a.N, a.C, a.H, a.W = N, C, H, W
+    rt = res = None
+    if isinstance(residual, NormTerm):
+        rt = residual
+        rx = _norm_check(rt, "residual", who, tuple(x.shape))
+        if rx.device != x.device:
+            raise _lib.MpiFlowHipError("%s: residual.x on %s must share term.x's device %s" % (who, rx.device, x.device))
+    elif residual is not None:
+        res = _gru_tensor(residual, "residual", who, tuple(x.shape), on_gpu=False)
+        if res.device != x.device:
+            raise _lib.MpiFlowHipError("%s: residual on %s must share term.x's device %s" % (who, res.device, x.device))
+        a.res = res.data_ptr()
+    if chunks is None:
+        chunks = norm_default_chunks(N * C, H * W)
+    if not isinstance(chunks, int) or not 1 <= chunks <= _lib.NORM_MAX_CHUNKS:
+        raise _lib.MpiFlowHipError("%s: chunks must be an integer in 1..%d (got %r)" % (who, _lib.NORM_MAX_CHUNKS, chunks))
+    a.chunks = chunks
+    if not x.is_cuda:
+        raise _lib.MpiFlowHipError("%s: term.x must live on the GPU (got %s); mpiflow_amd has no CPU path" % (who, x.device))
+    return a, x, rt, res
+
+
+@_on_device
+def norm_stats(x, mode, groups=1, chunks=None):
+    """mpf_norm_stats: float64 partials [N,C,chunks,2] = (mean, centred sum of squares) of every chunk of every plane of x, for a mode with statistics
+    ('instance', 'batch_train', 'group').  chunks=None: norm_default_chunks.  Hand it to NormTerm(partials=...); norm_act then uses its chunks."""
+    lib = _lib.load()
+    who = "norm_stats"
+    if mode in NORM_MODES and mode not in _NORM_STATS:
+        raise _lib.MpiFlowHipError("%s: mode '%s' has no statistics to compute" % (who, mode))
+    term = NormTerm(x, mode, groups=groups)
+    a, x, _, _ = _norm_args(term, None, who, chunks)
+    term.partials = torch.empty((x.shape[0], x.shape[1], a.chunks, 2), dtype=torch.float64, device=x.device)
+    _norm_fill(a.y, term)
+    _lib.check(lib.mpf_norm_stats(ctypes.byref(a), _stream()), "mpf_norm_stats")
+    return term.partials
+
+
+def _term_device(term):
+    """the device argument that makes _on_device select a NormTerm's GPU (it looks at tensors and devices, not into terms)"""
+    x = getattr(term, "x", None)
+    return x.device if isinstance(x, torch.Tensor) and x.is_cuda else None
+
+
+def norm_act(term, residual=None, chunks=None):
+    """mpf_norm_act: out = relu(norm(term.x)), or with a residual - a tensor, or a NormTerm, normalised without a ReLU - out =
+    relu(residual + relu(norm(term.x))).  Statistics a term lacks are computed first (one mpf_norm_stats launch for both terms); term.mean,
+    .rstd and .var are filled, .partials dropped.  float32, contiguous, on the GPU, or MpiFlowHipError.  Asynchronous on the current stream."""
+    return _norm_act(_term_device(term), term, residual, chunks)
+
+
+@_on_device
+def _norm_act(device, term, residual, chunks):
+    lib = _lib.load()
+    who = "norm_act"
+    given = [t.partials for t in (term, residual) if isinstance(t, NormTerm) and t.mode in _NORM_STATS and t.partials is not None]
+    if given:
+        if chunks is not None and chunks != given[0].shape[2]:
+            raise _lib.MpiFlowHipError("%s: chunks=%r but the partials handed in were computed with %d" % (who, chunks, given[0].shape[2]))
+        chunks = int(given[0].shape[2])
+    a, x, rt, res = _norm_args(term, residual, who, chunks)
+    N, C = x.shape[:2]
+    fresh = []
+    for t in (term, rt):
+        if t is None or t.mode not in _NORM_STATS:
+            continue
+        if t.partials is None:
+            t.partials = torch.empty((N, C, a.chunks, 2), dtype=torch.float64, device=x.device)
+            fresh.append(t)
+        elif tuple(t.partials.shape) != (N, C, a.chunks, 2) or t.partials.dtype != torch.float64 or not t.partials.is_contiguous() or t.partials.device != x.device:
+            raise _lib.MpiFlowHipError("%s: partials must be what norm_stats returned for this x with chunks=%d: float64 %s (got %s)"
+                                       % (who, a.chunks, [N, C, a.chunks, 2], tuple(t.partials.shape)))
+        stat = torch.empty((3, t.sets()), dtype=_f32, device=x.device)
+        t.mean, t.rstd, t.var = stat[0], stat[1], stat[2]
+    out = torch.empty_like(x)
+    a.out = out.data_ptr()
+    if fresh:
+        s = _lib.MpfNormArgs()
+        s.N, s.C, s.H, s.W, s.chunks = a.N, a.C, a.H, a.W, a.chunks
+        _norm_fill(s.y, fresh[0])
+        if len(fresh) > 1:
+            _norm_fill(s.r, fresh[1])
+        _lib.check(lib.mpf_norm_stats(ctypes.byref(s), _stream()), "mpf_norm_stats")
+    _norm_fill(a.y, term)
+    if rt is not None:
+        _norm_fill(a.r, rt)
+    _lib.check(lib.mpf_norm_act(ctypes.byref(a), _stream()), "mpf_norm_act")
+    for t in (term, rt):
+        if t is not None:
+            t.partials = None
+    return out
+
+
+def norm_act_backward(grad_out, term, residual=None, chunks=None, dres=None, param_grads=True):
+    """mpf_norm_act_backward_reduce + mpf_norm_act_backward: the cotangent of norm_act's out -> (dx, dweight, dbias, dresidual) for the same
+    term and residual, whose mean / rstd norm_act filled.  dresidual: the shortcut's gradient for a tensor residual - ADDED into `dres` when one
+    is given, otherwise written to a fresh tensor - or (dx, dweight, dbias) of a NormTerm residual, or None.  dweight / dbias are None where the
+    term has no weight / bias or param_grads is False ('batch_eval' then needs no reduce launch, like 'none').  Bit-identical from call to call."""
+    return _norm_act_backward(_term_device(term), grad_out, term, residual, chunks, dres, param_grads)
+
+
+@_on_device
+def _norm_act_backward(device, grad_out, term, residual, chunks, dres, param_grads):
+    lib = _lib.load()
+    who = "norm_act_backward"
+    a, x, rt, res = _norm_args(term, residual, who, chunks)
+    g = _gru_tensor(grad_out, "grad_out", who, tuple(x.shape))
+    if g.device != x.device:
+        raise _lib.MpiFlowHipError("%s: grad_out on %s must share term.x's device %s" % (who, g.device, x.device))
+    N, C = x.shape[:2]
+    a.g = g.data_ptr()
+    keep, results = [], []
+    for t, ct in ((term, a.y), (rt, a.r)):
+        if t is None:
+            continue
+        if t.mode in _NORM_STATS and (t.mean is None or t.rstd is None):
+            raise _lib.MpiFlowHipError("%s: the term has no mean / rstd: norm_act fills them in the forward pass" % who)
+        _norm_fill(ct, t)
+        dx = torch.empty_like(x)
+        dw = torch.empty_like(t.weight) if param_grads and t.mode != "none" and t.weight is not None else None
+        db = torch.empty_like(t.bias) if param_grads and t.mode != "none" and t.bias is not None else None
+        ct.dx = dx.data_ptr()
+        ct.dweight, ct.dbias = (None if dw is None else dw.data_ptr()), (None if db is None else db.data_ptr())
+        if t.mode in _NORM_STATS or dw is not None or db is not None:
+            gp = torch.empty((N, C, a.chunks, 2), dtype=torch.float64, device=x.device)
+            ct.grad_partials = gp.data_ptr()
+            keep.append(gp)
+        results.append((dx, dw, db))
+    if res is not None:
+        a.accumulate = int(dres is not None)
+        dres = torch.empty_like(x) if dres is None else _gru_tensor(dres, "dres", who, tuple(x.shape))
+        a.dres = dres.data_ptr()
+    if keep:
+        _lib.check(lib.mpf_norm_act_backward_reduce(ctypes.byref(a), _stream()), "mpf_norm_act_backward_reduce")
+    _lib.check(lib.mpf_norm_act_backward(ctypes.byref(a), _stream()), "mpf_norm_act_backward")
+    del keep
+    return results[0] + ((results[1] if rt is not None else dres),)
+
+
 @_on_device
 def to_u8_bgr(img_3HW):
     lib = _lib.load()
