@@ -21,6 +21,7 @@
 // the fast-math forms (__expf, a tanh from one __expf) are not used: their absolute error near saturation is several ulp of 1, beyond 3 x the
 // fp32 run's own error that the tests allow.  No address depends on a tensor's values: NaN and inf travel through the arithmetic as in torch.
 #include "mpf_common.h"
+#include "mpf_math.h"
 
 #define GRU_THREADS 256
 #define GRU_MAX_BLOCKS 2048
@@ -41,26 +42,6 @@ struct GruDev {
     int C, HW, total;            // total: lanes of work = B * C * HW / VEC
 };
 
-template <int VEC>
-__device__ __forceinline__ void gru_load(const float *p, float (&v)[VEC])
-{
-    if constexpr (VEC == 4) {
-        const float4 t = *(const float4 *)p;
-        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-    } else {
-        v[0] = *p;
-    }
-}
-
-template <int VEC>
-__device__ __forceinline__ void gru_store(float *p, const float (&v)[VEC])
-{
-    if constexpr (VEC == 4)
-        *(float4 *)p = make_float4(v[0], v[1], v[2], v[3]);
-    else
-        *p = v[0];
-}
-
 // the sum of the present terms, in term order; the launcher guarantees that one is present
 template <int VEC>
 __device__ __forceinline__ void gru_sum(const GruSlice (&t)[MPF_GRU_MAX_TERMS], int b, int off, float (&s)[VEC])
@@ -70,7 +51,7 @@ __device__ __forceinline__ void gru_sum(const GruSlice (&t)[MPF_GRU_MAX_TERMS], 
     for (int k = 0; k < MPF_GRU_MAX_TERMS; ++k) {
         if (!t[k].p) continue;                                // uniform: a kernel argument
         float v[VEC];
-        gru_load<VEC>(t[k].p + (size_t)b * t[k].bstride + off, v);
+        mpf_load_vec<VEC>(t[k].p + (size_t)b * t[k].bstride + off, v);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) s[e] = first ? v[e] : s[e] + v[e];
         first = false;
@@ -82,7 +63,7 @@ __device__ __forceinline__ void gru_store_slices(const GruSlice (&d)[2], int b, 
 {
 #pragma unroll
     for (int k = 0; k < 2; ++k)
-        if (d[k].p) gru_store<VEC>(d[k].p + (size_t)b * d[k].bstride + off, v);
+        if (d[k].p) mpf_store_vec<VEC>(d[k].p + (size_t)b * d[k].bstride + off, v);
 }
 
 __device__ __forceinline__ float gru_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
@@ -98,19 +79,19 @@ __global__ __launch_bounds__(GRU_THREADS) void k_gru(const GruDev a)
         const int off = c * a.HW + i;                         // inside one sample of a slice
         const size_t flat = (size_t)plane * a.HW + i;         // inside a [B,C,H,W] tensor
         float h[VEC], o[VEC];
-        gru_load<VEC>(a.h + flat, h);
+        mpf_load_vec<VEC>(a.h + flat, h);
         if (MODE == GRU_RESET) {
             float s[VEC];
             gru_sum<VEC>(a.r, b, off, s);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) o[e] = gru_sigmoid(s[e]) * h[e];
-            gru_store<VEC>(a.out + flat, o);
+            mpf_store_vec<VEC>(a.out + flat, o);
         } else if (MODE == GRU_RESET_BWD) {
             float s[VEC], g[VEC], dr[VEC], dh[VEC];
             gru_sum<VEC>(a.r, b, off, s);
-            gru_load<VEC>(a.g + flat, g);
+            mpf_load_vec<VEC>(a.g + flat, g);
             if (a.accumulate) {
-                gru_load<VEC>(a.dh + flat, dh);
+                mpf_load_vec<VEC>(a.dh + flat, dh);
             } else {
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) dh[e] = 0.0f;
@@ -122,7 +103,7 @@ __global__ __launch_bounds__(GRU_THREADS) void k_gru(const GruDev a)
                 dh[e] = a.accumulate ? dh[e] + g[e] * r : g[e] * r;
             }
             gru_store_slices<VEC>(a.dr, b, off, dr);
-            gru_store<VEC>(a.dh + flat, dh);
+            mpf_store_vec<VEC>(a.dh + flat, dh);
         } else {
             float sz[VEC], sq[VEC];
             gru_sum<VEC>(a.z, b, off, sz);
@@ -133,10 +114,10 @@ __global__ __launch_bounds__(GRU_THREADS) void k_gru(const GruDev a)
                     const float z = gru_sigmoid(sz[e]), q = tanhf(sq[e]);
                     o[e] = (1.0f - z) * h[e] + z * q;
                 }
-                gru_store<VEC>(a.out + flat, o);
+                mpf_store_vec<VEC>(a.out + flat, o);
             } else {
                 float g[VEC], dz[VEC], dq[VEC], dh[VEC];
-                gru_load<VEC>(a.g + flat, g);
+                mpf_load_vec<VEC>(a.g + flat, g);
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) {
                     const float z = gru_sigmoid(sz[e]), q = tanhf(sq[e]);
@@ -146,7 +127,7 @@ __global__ __launch_bounds__(GRU_THREADS) void k_gru(const GruDev a)
                 }
                 gru_store_slices<VEC>(a.dz, b, off, dz);
                 gru_store_slices<VEC>(a.dq, b, off, dq);
-                gru_store<VEC>(a.dh + flat, dh);
+                mpf_store_vec<VEC>(a.dh + flat, dh);
             }
         }
     }

@@ -222,6 +222,27 @@ MPF_DEV uint8_t mpf_to_u8(float v)
     return (uint8_t)r;
 }
 
+// VEC consecutive floats at p: one 16-byte access (VEC == 4; p 16-byte aligned) or one float (VEC == 1)
+template <int VEC>
+MPF_DEV void mpf_load_vec(const float *p, float (&v)[VEC])
+{
+    if constexpr (VEC == 4) {
+        const float4 t = *(const float4 *)p;
+        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+    } else {
+        v[0] = *p;
+    }
+}
+
+template <int VEC>
+MPF_DEV void mpf_store_vec(float *p, const float (&v)[VEC])
+{
+    if constexpr (VEC == 4)
+        *(float4 *)p = make_float4(v[0], v[1], v[2], v[3]);
+    else
+        *p = v[0];
+}
+
 // XCD-aware block remap (MI355X: 8 XCDs, block b is dispatched to XCD b % 8, each XCD has a private 4 MiB L2).
 // Gives XCD k the k-th contiguous chunk of the logical tile order so that neighbouring tiles (which share source
 // texel rows) hit the same L2.  Bijective for any grid size.  A pure speed choice: correctness never depends on it.

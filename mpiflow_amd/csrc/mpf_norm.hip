@@ -25,6 +25,7 @@
 // Numerics: eps = 1e-5.  relu(v) = v < 0 ? 0 : v (fmaxf would turn NaN into 0, torch keeps it), and the gradient passes where !(v <= 0), which
 // is torch's threshold_backward.  No address depends on a tensor's values.
 #include "mpf_common.h"
+#include "mpf_math.h"
 
 #define NORM_THREADS 256
 #define NORM_WAVES (NORM_THREADS / 64)
@@ -152,26 +153,6 @@ __device__ __forceinline__ void norm_block_sum(double (&v)[K], NormShared &sh)
     }
 }
 
-template <int VEC>
-__device__ __forceinline__ void norm_load(const float *p, float (&v)[VEC])
-{
-    if constexpr (VEC == 4) {
-        const float4 t = *(const float4 *)p;
-        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-    } else {
-        v[0] = *p;
-    }
-}
-
-template <int VEC>
-__device__ __forceinline__ void norm_store(float *p, const float (&v)[VEC])
-{
-    if constexpr (VEC == 4)
-        *(float4 *)p = make_float4(v[0], v[1], v[2], v[3]);
-    else
-        *p = v[0];
-}
-
 __device__ __forceinline__ float norm_relu(float v) { return v < 0.0f ? 0.0f : v; }
 
 __device__ __forceinline__ float norm_xhat(float x, const NormCoef &c) { return (x - c.mean) * c.rstd; }
@@ -206,7 +187,7 @@ __global__ __launch_bounds__(NORM_THREADS) void k_norm_stats(const NormDev a)
     double s[2] = {0.0, 0.0};
     for (int i = threadIdx.x * VEC; i < count; i += NORM_THREADS * VEC) {
         float v[VEC];
-        norm_load<VEC>(p + i, v);
+        mpf_load_vec<VEC>(p + i, v);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             const double d = (double)v[e] - shift;
@@ -248,11 +229,11 @@ __global__ __launch_bounds__(NORM_THREADS) void k_norm_act(const NormDev a)
     const size_t base = (size_t)plane * a.HW + (size_t)k * a.L;
     for (int i = threadIdx.x * VEC; i < count; i += NORM_THREADS * VEC) {
         float x[VEC], r[VEC], o[VEC];
-        norm_load<VEC>(a.t[0].x + base + i, x);
+        mpf_load_vec<VEC>(a.t[0].x + base + i, x);
         if (has_r)
-            norm_load<VEC>(a.t[1].x + base + i, r);
+            mpf_load_vec<VEC>(a.t[1].x + base + i, r);
         else if (a.res)
-            norm_load<VEC>(a.res + base + i, r);
+            mpf_load_vec<VEC>(a.res + base + i, r);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             const float y = norm_relu(norm_value(x[e], co[0], a.t[0].mode));
@@ -263,7 +244,7 @@ __global__ __launch_bounds__(NORM_THREADS) void k_norm_act(const NormDev a)
             else
                 o[e] = y;
         }
-        norm_store<VEC>(a.out + base + i, o);
+        mpf_store_vec<VEC>(a.out + base + i, o);
     }
 }
 
@@ -289,12 +270,12 @@ __global__ __launch_bounds__(NORM_THREADS) void k_norm_bwd_reduce(const NormDev 
     double s[4] = {0.0, 0.0, 0.0, 0.0};
     for (int i = threadIdx.x * VEC; i < count; i += NORM_THREADS * VEC) {
         float x[VEC], r[VEC], g[VEC];
-        norm_load<VEC>(a.t[0].x + base + i, x);
-        norm_load<VEC>(a.g + base + i, g);
+        mpf_load_vec<VEC>(a.t[0].x + base + i, x);
+        mpf_load_vec<VEC>(a.g + base + i, g);
         if (has_r)
-            norm_load<VEC>(a.t[1].x + base + i, r);
+            mpf_load_vec<VEC>(a.t[1].x + base + i, r);
         else if (a.res)
-            norm_load<VEC>(a.res + base + i, r);
+            mpf_load_vec<VEC>(a.res + base + i, r);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             const float rv = has_r ? norm_value(r[e], co[1], a.t[1].mode) : (a.res ? r[e] : 0.0f);
@@ -373,13 +354,13 @@ __global__ __launch_bounds__(NORM_THREADS) void k_norm_bwd(const NormDev a)
     const size_t base = (size_t)plane * a.HW + (size_t)k * a.L;
     for (int i = threadIdx.x * VEC; i < count; i += NORM_THREADS * VEC) {
         float x[VEC], r[VEC], g[VEC], d0[VEC], d1[VEC];
-        norm_load<VEC>(a.t[0].x + base + i, x);
-        norm_load<VEC>(a.g + base + i, g);
+        mpf_load_vec<VEC>(a.t[0].x + base + i, x);
+        mpf_load_vec<VEC>(a.g + base + i, g);
         if (has_r)
-            norm_load<VEC>(a.t[1].x + base + i, r);
+            mpf_load_vec<VEC>(a.t[1].x + base + i, r);
         else if (a.res)
-            norm_load<VEC>(a.res + base + i, r);
-        if (a.res && a.accumulate) norm_load<VEC>(a.dres + base + i, d1);
+            mpf_load_vec<VEC>(a.res + base + i, r);
+        if (a.res && a.accumulate) mpf_load_vec<VEC>(a.dres + base + i, d1);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             const float rv = has_r ? norm_value(r[e], co[1], a.t[1].mode) : (a.res ? r[e] : 0.0f);
@@ -391,11 +372,11 @@ __global__ __launch_bounds__(NORM_THREADS) void k_norm_bwd(const NormDev a)
             else if (a.res)
                 d1[e] = a.accumulate ? d1[e] + g2 : g2;
         }
-        norm_store<VEC>(a.t[0].dx + base + i, d0);
+        mpf_store_vec<VEC>(a.t[0].dx + base + i, d0);
         if (has_r)
-            norm_store<VEC>(a.t[1].dx + base + i, d1);
+            mpf_store_vec<VEC>(a.t[1].dx + base + i, d1);
         else if (a.res)
-            norm_store<VEC>(a.dres + base + i, d1);
+            mpf_store_vec<VEC>(a.dres + base + i, d1);
     }
 }
 

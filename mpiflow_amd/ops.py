@@ -9,6 +9,7 @@ import ctypes
 import torch
 
 from . import _lib, host_math
+from ._tensors import check_devices, check_pyramid, check_tensor
 
 _f32 = torch.float32
 
@@ -702,44 +703,28 @@ def photometric_pairs(samples, out=None):
     return out
 
 
-def _corr_tensor(t, name, ndim, who="corr_lookup", device_last=False):
-    """RAFT's correlation lookups take their tensors as they are: no silent copy, cast or move.  device_last: dtype and layout are judged
-    before the device, so that each refusal can be had without a GPU."""
-    if not isinstance(t, torch.Tensor):
-        raise _lib.MpiFlowHipError("%s: %s must be a torch.Tensor (got %s)" % (who, name, type(t).__name__))
-    if not t.is_cuda and not device_last:
-        raise _lib.MpiFlowHipError("%s: %s must live on the GPU (got %s); mpiflow_amd has no CPU path" % (who, name, t.device))
-    if t.dtype != _f32:
-        raise _lib.MpiFlowHipError("%s: %s must be float32 (got %s)" % (who, name, t.dtype))
-    if t.dim() != ndim:
-        raise _lib.MpiFlowHipError("%s: %s must have %d dimensions (got shape %s)" % (who, name, ndim, tuple(t.shape)))
-    if not t.is_contiguous():
-        raise _lib.MpiFlowHipError("%s: %s must be contiguous" % (who, name))
-    if not t.is_cuda:
-        raise _lib.MpiFlowHipError("%s: %s must live on the GPU (got %s); mpiflow_amd has no CPU path" % (who, name, t.device))
-    return t
-
-
-def _corr_args(fmap1_nhwc, f2_levels_nhwc, coords, radius, scale, plain=False):
-    f1 = _corr_tensor(fmap1_nhwc, "fmap1_nhwc", 4)
+def _corr_args(fmap1_nhwc, f2_levels_nhwc, coords, radius, scale, who, plain=False, out=None, out_name="out"):
+    """MpfCorrArgs of an on-demand lookup, with `out` (or grad_out) if the caller has one, and the levels as a list"""
+    f1 = check_tensor(fmap1_nhwc, "fmap1_nhwc", who, 4, "[B,H,W,C]")
     B, H, W, C = f1.shape
     levels = list(f2_levels_nhwc)
-    if not 1 <= len(levels) <= _lib.CORR_MAX_LEVELS:
-        raise _lib.MpiFlowHipError("corr_lookup: num_levels must be 1..%d (got %d)" % (_lib.CORR_MAX_LEVELS, len(levels)))
-    co = _corr_tensor(coords, "coords", 4)
-    if tuple(co.shape) != (B, 2, H, W):
-        raise _lib.MpiFlowHipError("corr_lookup: coords must be [B,2,H,W] = %s (got %s)" % ((B, 2, H, W), tuple(co.shape)))
+    check_pyramid(who, None, None, len(levels))
+    co = check_tensor(coords, "coords", who, (B, 2, H, W), "[B,2,H,W] = %s" % ((B, 2, H, W),))
     a = _lib.MpfCorrArgs()
     a.fmap1, a.coords = f1.data_ptr(), co.data_ptr()
     a.B, a.C, a.H, a.W = B, C, H, W
+    tensors = dict(fmap1_nhwc=f1, coords=co)
     for i, t in enumerate(levels):
-        t = _corr_tensor(t, "f2_levels_nhwc[%d]" % i, 4)
-        if t.shape[0] != B or t.shape[3] != C or t.device != f1.device:
-            raise _lib.MpiFlowHipError("corr_lookup: f2_levels_nhwc[%d] is %s on %s for fmap1_nhwc %s on %s" % (i, tuple(t.shape), t.device, tuple(f1.shape), f1.device))
+        tensors["f2_levels_nhwc[%d]" % i] = check_tensor(t, "f2_levels_nhwc[%d]" % i, who, (B, None, None, C), "[B,H_i,W_i,C] for fmap1_nhwc %s" % (tuple(f1.shape),))
         a.f2[i], a.Hl[i], a.Wl[i] = t.data_ptr(), t.shape[1], t.shape[2]
     a.radius, a.levels = int(radius), len(levels)
     a.scale = 1.0 / float(torch.sqrt(torch.tensor(C).float())) if scale is None else float(scale)       # RAFT divides by the fp32 sqrt(C)
     a.plain = int(bool(plain))
+    if out is not None:
+        rd = 2 * a.radius + 1
+        tensors[out_name] = check_tensor(out, out_name, who, (B, len(levels) * rd * rd, H, W))
+        a.out = out.data_ptr()
+    check_devices(who, tensors)
     return a, levels
 
 
@@ -749,15 +734,12 @@ def corr_lookup(fmap1_nhwc, f2_levels_nhwc, coords, radius, out=None, scale=None
     fmap1_nhwc [B,H,W,C], f2_levels_nhwc: level i of fmap2's avg_pool2d pyramid as [B,H_i,W_i,C], coords [B,2,H,W] (x, y; any value is
     legal, non-finite ones give 0) -> [B, L*(2r+1)^2, H, W], scaled by `scale` (default 1/sqrt(C)).  float32, contiguous, on the GPU, or
     MpiFlowHipError.  `plain`: the one-thread-per-entry form of the kernel (yardstick of tools/bench_corr.py).  Asynchronous on the current stream."""
+    a, levels = _corr_args(fmap1_nhwc, f2_levels_nhwc, coords, radius, scale, "corr_lookup", plain, out)
     lib = _lib.load()
-    a, levels = _corr_args(fmap1_nhwc, f2_levels_nhwc, coords, radius, scale, plain)
-    rd = 2 * int(radius) + 1
-    shape = (a.B, len(levels) * rd * rd, a.H, a.W)
     if out is None:
-        out = torch.empty(shape, dtype=_f32, device=fmap1_nhwc.device)
-    elif tuple(_corr_tensor(out, "out", 4).shape) != shape or out.device != fmap1_nhwc.device:
-        raise _lib.MpiFlowHipError("corr_lookup: out must be %s on %s" % (shape, fmap1_nhwc.device))
-    a.out = out.data_ptr()
+        rd = 2 * a.radius + 1
+        out = torch.empty((a.B, len(levels) * rd * rd, a.H, a.W), dtype=_f32, device=fmap1_nhwc.device)
+        a.out = out.data_ptr()
     _lib.check(lib.mpf_corr_lookup(ctypes.byref(a), _stream()), "mpf_corr_lookup")
     return out
 
@@ -767,84 +749,49 @@ def corr_lookup_backward(fmap1_nhwc, f2_levels_nhwc, coords, grad_out, radius, s
     """mpf_corr_lookup_backward: the cotangent grad_out [B, L*(2r+1)^2, H, W] of corr_lookup -> (grad_fmap1_nhwc, [grad_f2_i_nhwc per level]).
     grad_fmap1 is a per-pixel sum (bit-identical from run to run); the levels' gradients are scattered with fp32 atomics (last bits vary).
     There is no gradient for coords.  Asynchronous on the current stream."""
+    if grad_out is None:
+        raise _lib.MpiFlowHipError("corr_lookup_backward: grad_out must be a torch.Tensor (got NoneType)")
+    a, levels = _corr_args(fmap1_nhwc, f2_levels_nhwc, coords, radius, scale, "corr_lookup_backward", out=grad_out, out_name="grad_out")
     lib = _lib.load()
-    a, levels = _corr_args(fmap1_nhwc, f2_levels_nhwc, coords, radius, scale)
-    rd = 2 * int(radius) + 1
-    shape = (a.B, len(levels) * rd * rd, a.H, a.W)
-    if tuple(_corr_tensor(grad_out, "grad_out", 4).shape) != shape:
-        raise _lib.MpiFlowHipError("corr_lookup_backward: grad_out must be %s (got %s)" % (shape, tuple(grad_out.shape)))
     g1 = torch.empty_like(fmap1_nhwc)
     g2 = [torch.zeros_like(t) for t in levels]
-    a.out, a.grad_fmap1 = grad_out.data_ptr(), g1.data_ptr()
+    a.grad_fmap1 = g1.data_ptr()
     for i, t in enumerate(g2):
         a.grad_f2[i] = t.data_ptr()
     _lib.check(lib.mpf_corr_lookup_backward(ctypes.byref(a), _stream()), "mpf_corr_lookup_backward")
     return g1, g2
 
 
-def _corr_volume_tensor(t, name, ndim, who):
-    """dtype and layout of one tensor of the all-pairs calls, taken as it is: no silent copy or cast.  The device is judged by
-    _corr_volume_args, after the shapes."""
-    if not isinstance(t, torch.Tensor):
-        raise _lib.MpiFlowHipError("%s: %s must be a torch.Tensor (got %s)" % (who, name, type(t).__name__))
-    if t.dtype != _f32:
-        raise _lib.MpiFlowHipError("%s: %s must be float32 (got %s)" % (who, name, t.dtype))
-    if t.dim() != ndim:
-        raise _lib.MpiFlowHipError("%s: %s must have %d dimensions (got shape %s)" % (who, name, ndim, tuple(t.shape)))
-    if not t.is_contiguous():
-        raise _lib.MpiFlowHipError("%s: %s must be contiguous" % (who, name))
-    return t
-
-
-def _corr_volume_frame(level0, num_levels, who):
-    """(N, H, W) of level 0 [N, H, W]: N = B * H * W rows, every level of the pooled pyramid at least 2 x 2"""
-    N, H, W = level0.shape
-    if H * W == 0 or N == 0 or N % (H * W):
-        raise _lib.MpiFlowHipError("%s: level 0 %s must hold B * H * W rows of H x W" % (who, tuple(level0.shape)))
-    if min(H, W) < 2 ** num_levels:
-        raise _lib.MpiFlowHipError("%s: H, W = %d, %d must be at least 2^num_levels = %d (every level at least 2 x 2)" % (who, H, W, 2 ** num_levels))
-    return N, H, W
+def _corr_volume_rows(who, N, H, W):
+    """level 0 [N, H, W] of an all-pairs pyramid holds N = B * H * W rows"""
+    if N == 0 or N % (H * W):
+        raise _lib.MpiFlowHipError("%s: level 0 %s must hold B * H * W rows of H x W" % (who, (N, H, W)))
 
 
 def _corr_volume_args(levels, who, norm=None, coords=None, radius=None, out=None, out_name="out"):
     """MpfCorrVolumeArgs for a pyramid (or its gradient): levels[i] [N, H >> i, W >> i] with N = B*H*W rows, for a pyramid call (norm) or a
-    lookup call (coords [B,2,H,W], radius, and out / grad_out [B, L*(2r+1)^2, H, W] if the caller has one).  The C ABI sees bare pointers:
-    these comparisons are what ties every tensor's real size to what the kernels index.  Order: dtype and layout, then every shape, the
-    device last (a wrong shape is reported as such wherever the tensors live)."""
+    lookup call (coords [B,2,H,W], radius, and out / grad_out [B, L*(2r+1)^2, H, W] if the caller has one)."""
     levels = list(levels)
-    if not 1 <= len(levels) <= _lib.CORR_MAX_LEVELS:
-        raise _lib.MpiFlowHipError("%s: num_levels must be 1..%d (got %d)" % (who, _lib.CORR_MAX_LEVELS, len(levels)))
-    tensors = [("levels[%d]" % i, _corr_volume_tensor(t, "levels[%d]" % i, 3, who)) for i, t in enumerate(levels)]
-    N, H, W = _corr_volume_frame(levels[0], len(levels), who)
+    N, H, W = check_tensor(levels[0], "levels[0]", who, 3).shape if levels else (0, 0, 0)
+    check_pyramid(who, H, W, len(levels), radius)               # an empty list is refused here
+    _corr_volume_rows(who, N, H, W)
     a = _lib.MpfCorrVolumeArgs()
+    tensors = {}
     for i, t in enumerate(levels):
-        if tuple(t.shape) != (N, H >> i, W >> i):
-            raise _lib.MpiFlowHipError("%s: levels[%d] must be %s, level %d of a pooled pyramid of %d rows of %d x %d (got %s)"
-                                       % (who, i, (N, H >> i, W >> i), i, N, H, W, tuple(t.shape)))
+        tensors["levels[%d]" % i] = check_tensor(t, "levels[%d]" % i, who, (N, H >> i, W >> i),
+                                                 "%s, level %d of a pooled pyramid of %d rows of %d x %d" % ((N, H >> i, W >> i), i, N, H, W))
         a.level[i], a.Hl[i], a.Wl[i] = t.data_ptr(), H >> i, W >> i
     a.B, a.H, a.W, a.levels = N // (H * W), H, W, len(levels)
     if coords is None:
         a.norm = float(norm)
     else:
-        if not 1 <= int(radius) <= 8:
-            raise _lib.MpiFlowHipError("%s: radius must be 1..8 (got %s)" % (who, radius))
-        co = _corr_volume_tensor(coords, "coords", 4, who)
-        if tuple(co.shape) != (a.B, 2, H, W):
-            raise _lib.MpiFlowHipError("%s: coords must be [B,2,H,W] = %s for %d rows of %d x %d (got %s)" % (who, (a.B, 2, H, W), N, H, W, tuple(co.shape)))
-        tensors.append(("coords", co))
+        co = tensors["coords"] = check_tensor(coords, "coords", who, (a.B, 2, H, W), "[B,2,H,W] = %s for %d rows of %d x %d" % ((a.B, 2, H, W), N, H, W))
         a.coords, a.radius = co.data_ptr(), int(radius)
         if out is not None:
-            rd = 2 * int(radius) + 1
-            shape = (a.B, len(levels) * rd * rd, H, W)
-            if tuple(_corr_volume_tensor(out, out_name, 4, who).shape) != shape:
-                raise _lib.MpiFlowHipError("%s: %s must be %s (got %s)" % (who, out_name, shape, tuple(out.shape)))
-            tensors.append((out_name, out))
+            rd = 2 * a.radius + 1
+            tensors[out_name] = check_tensor(out, out_name, who, (a.B, len(levels) * rd * rd, H, W))
             a.out = out.data_ptr()
-    for name, t in tensors:
-        if not t.is_cuda:
-            raise _lib.MpiFlowHipError("%s: %s must live on the GPU (got %s); mpiflow_amd has no CPU path" % (who, name, t.device))
-        if t.device != levels[0].device:
-            raise _lib.MpiFlowHipError("%s: %s is on %s, levels[0] on %s" % (who, name, t.device, levels[0].device))
+    check_devices(who, tensors)
     return a, levels
 
 
@@ -853,16 +800,14 @@ def corr_pyramid(raw, num_levels, norm):
     """mpf_corr_pyramid: raw [B*H*W, H, W], the product fmap1^T fmap2 (row p: query pixel p against all of frame 2) -> the list of num_levels
     levels [B*H*W, H >> i, W >> i] of CorrBlock's pyramid.  Level 0 IS raw, divided by `norm` (RAFT: sqrt(C) in float32) in place; the other
     levels are new.  float32, contiguous, on the GPU, or MpiFlowHipError.  Asynchronous on the current stream."""
-    lib = _lib.load()
-    raw = _corr_volume_tensor(raw, "raw", 3, "corr_pyramid")
-    if not 1 <= int(num_levels) <= _lib.CORR_MAX_LEVELS:
-        raise _lib.MpiFlowHipError("corr_pyramid: num_levels must be 1..%d (got %s)" % (_lib.CORR_MAX_LEVELS, num_levels))
-    N, H, W = _corr_volume_frame(raw, int(num_levels), "corr_pyramid")
-    if not raw.is_cuda:
-        raise _lib.MpiFlowHipError("corr_pyramid: raw must live on the GPU (got %s); mpiflow_amd has no CPU path" % raw.device)
+    who = "corr_pyramid"
+    N, H, W = check_tensor(raw, "raw", who, 3).shape
+    check_pyramid(who, H, W, num_levels)
+    _corr_volume_rows(who, N, H, W)
+    check_devices(who, dict(raw=raw))
     levels = [raw] + [torch.empty((N, H >> i, W >> i), dtype=_f32, device=raw.device) for i in range(1, int(num_levels))]
-    a, levels = _corr_volume_args(levels, "corr_pyramid", norm=norm)
-    _lib.check(lib.mpf_corr_pyramid(ctypes.byref(a), _stream()), "mpf_corr_pyramid")
+    a, levels = _corr_volume_args(levels, who, norm=norm)
+    _lib.check(_lib.load().mpf_corr_pyramid(ctypes.byref(a), _stream()), "mpf_corr_pyramid")
     return levels
 
 
@@ -870,13 +815,12 @@ def corr_pyramid(raw, num_levels, norm):
 def corr_volume_lookup(levels, coords, radius, out=None):
     """mpf_corr_volume_lookup: CorrBlock's lookup, every level in one launch.  levels: corr_pyramid's result, coords [B,2,H,W] (x, y; any value
     is legal, non-finite ones give 0) -> [B, L*(2r+1)^2, H, W].  Asynchronous on the current stream."""
-    lib = _lib.load()
     a, levels = _corr_volume_args(levels, "corr_volume_lookup", coords=coords, radius=radius, out=out)
     if out is None:
         rd = 2 * int(radius) + 1
         out = torch.empty((a.B, len(levels) * rd * rd, a.H, a.W), dtype=_f32, device=coords.device)
         a.out = out.data_ptr()
-    _lib.check(lib.mpf_corr_volume_lookup(ctypes.byref(a), _stream()), "mpf_corr_volume_lookup")
+    _lib.check(_lib.load().mpf_corr_volume_lookup(ctypes.byref(a), _stream()), "mpf_corr_volume_lookup")
     return out
 
 
@@ -885,11 +829,10 @@ def corr_volume_lookup_backward(grad_levels, coords, grad_out, radius):
     """mpf_corr_volume_lookup_backward: ADDS the gradient of one lookup with the cotangent grad_out [B, L*(2r+1)^2, H, W] into grad_levels, a
     gradient pyramid shaped like corr_pyramid's result that the caller zeroed once and may share between lookups.  No atomics: bit-identical
     from run to run.  Returns grad_levels.  Asynchronous on the current stream."""
-    lib = _lib.load()
     if grad_out is None:
         raise _lib.MpiFlowHipError("corr_volume_lookup_backward: grad_out must be a torch.Tensor (got NoneType)")
     a, grad_levels = _corr_volume_args(grad_levels, "corr_volume_lookup_backward", coords=coords, radius=radius, out=grad_out, out_name="grad_out")
-    _lib.check(lib.mpf_corr_volume_lookup_backward(ctypes.byref(a), _stream()), "mpf_corr_volume_lookup_backward")
+    _lib.check(_lib.load().mpf_corr_volume_lookup_backward(ctypes.byref(a), _stream()), "mpf_corr_volume_lookup_backward")
     return grad_levels
 
 
@@ -897,54 +840,26 @@ def corr_volume_lookup_backward(grad_levels, coords, grad_out, radius):
 def corr_pyramid_backward(grad_levels, norm):
     """mpf_corr_pyramid_backward: folds a gradient pyramid into the gradient of the raw product, in place in grad_levels[0], which it returns
     ([B*H*W, H, W]); the other levels are only read.  Asynchronous on the current stream."""
-    lib = _lib.load()
     a, grad_levels = _corr_volume_args(grad_levels, "corr_pyramid_backward", norm=norm)
-    _lib.check(lib.mpf_corr_pyramid_backward(ctypes.byref(a), _stream()), "mpf_corr_pyramid_backward")
+    _lib.check(_lib.load().mpf_corr_pyramid_backward(ctypes.byref(a), _stream()), "mpf_corr_pyramid_backward")
     return grad_levels[0]
 
 
-def _up_tensor(t, name, shape, who):
-    """RAFT's upsampling takes its tensors as they are: no silent copy, cast or move.  `shape`: None entries are free."""
-    if not isinstance(t, torch.Tensor):
-        raise _lib.MpiFlowHipError("%s: %s must be a torch.Tensor (got %s)" % (who, name, type(t).__name__))
-    if t.dtype != _f32:
-        hint = "; call .float() on it (a half-precision kernel does not exist)" if t.dtype in (torch.float16, torch.bfloat16) else ""
-        raise _lib.MpiFlowHipError("%s: %s must be float32 (got %s)%s" % (who, name, t.dtype, hint))
-    if t.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, t.shape)):
-        raise _lib.MpiFlowHipError("%s: %s must be %s (got shape %s)" % (who, name, list(shape), tuple(t.shape)))
-    if not t.is_contiguous():
-        raise _lib.MpiFlowHipError("%s: %s must be contiguous" % (who, name))
-    return t
-
-
-def _up_on_gpu(who, **tensors):
-    """after every tensor's own checks, so that a wrong dtype or shape is named as such on any device"""
-    first = None
-    for name, t in tensors.items():
-        if not t.is_cuda:
-            raise _lib.MpiFlowHipError("%s: %s must live on the GPU (got %s); mpiflow_amd has no CPU path" % (who, name, t.device))
-        first = t.device if first is None else first
-        if t.device != first:
-            raise _lib.MpiFlowHipError("%s: %s on %s must share flow's device %s" % (who, name, t.device, first))
-
-
-def _up_args(flow, mask, who, **more):
-    f = _up_tensor(flow, "flow", (None, 2, None, None), who)
+def _up_args(flow, mask, who):
+    """MpfUpsampleArgs with flow [N,2,H,W] and mask [N,576,H,W]; the caller checks its other tensors against N, H, W, then the devices"""
+    f = check_tensor(flow, "flow", who, (None, 2, None, None))
     N, _, H, W = f.shape
-    m = _up_tensor(mask, "mask", (N, 576, H, W), who)
-    _up_on_gpu(who, flow=f, mask=m, **more)
+    m = check_tensor(mask, "mask", who, (N, 576, H, W))
     a = _lib.MpfUpsampleArgs()
     a.flow, a.mask, a.N, a.H, a.W = f.data_ptr(), m.data_ptr(), N, H, W
     return a
 
 
 def _up_loss_args(flow, mask, flow_gt, valid, max_flow, who, **more):
-    N, H, W = (tuple(flow.shape[i] for i in (0, 2, 3)) if isinstance(flow, torch.Tensor) and flow.dim() == 4 else (None, None, None))
-    _up_tensor(flow, "flow", (None, 2, None, None), who)
-    _up_tensor(mask, "mask", (N, 576, H, W), who)
-    gt = _up_tensor(flow_gt, "flow_gt", (N, 2, 8 * H, 8 * W), who)
-    va = _up_tensor(valid, "valid", (N, 8 * H, 8 * W), who)
-    a = _up_args(flow, mask, who, flow_gt=gt, valid=va, **more)
+    a = _up_args(flow, mask, who)
+    gt = check_tensor(flow_gt, "flow_gt", who, (a.N, 2, 8 * a.H, 8 * a.W))
+    va = check_tensor(valid, "valid", who, (a.N, 8 * a.H, 8 * a.W))
+    check_devices(who, dict(flow=flow, mask=mask, flow_gt=gt, valid=va, **more))
     a.flow_gt, a.valid, a.max_flow = gt.data_ptr(), va.data_ptr(), float(max_flow)
     return a
 
@@ -959,11 +874,11 @@ def _up_workspace(lib, a, backward, dev):
 def upsample_flow(flow, mask):
     """mpf_upsample_flow: RAFT's convex upsampling.  flow [N,2,H,W], mask [N,576,H,W] -> [N,2,8H,8W]: per fine pixel the softmax over the mask's
     9 taps blends the 3 x 3 neighbourhood of 8 * flow.  float32, contiguous, on the GPU, or MpiFlowHipError.  Asynchronous on the current stream."""
-    lib = _lib.load()
     a = _up_args(flow, mask, "upsample_flow")
+    check_devices("upsample_flow", dict(flow=flow, mask=mask))
     out = torch.empty((a.N, 2, 8 * a.H, 8 * a.W), dtype=_f32, device=flow.device)
     a.out = out.data_ptr()
-    _lib.check(lib.mpf_upsample_flow(ctypes.byref(a), _stream()), "mpf_upsample_flow")
+    _lib.check(_lib.load().mpf_upsample_flow(ctypes.byref(a), _stream()), "mpf_upsample_flow")
     return out
 
 
@@ -971,11 +886,11 @@ def upsample_flow(flow, mask):
 def upsample_flow_backward(flow, mask, grad_out):
     """mpf_upsample_flow_backward: the cotangent grad_out [N,2,8H,8W] of upsample_flow -> (grad_flow, grad_mask); the softmax is recomputed, no
     atomics: bit-identical from run to run.  Asynchronous on the current stream."""
+    who = "upsample_flow_backward"
+    a = _up_args(flow, mask, who)
+    g = check_tensor(grad_out, "grad_out", who, (a.N, 2, 8 * a.H, 8 * a.W))
+    check_devices(who, dict(flow=flow, mask=mask, grad_out=g))
     lib = _lib.load()
-    g = _up_tensor(grad_out, "grad_out", (None, 2, None, None), "upsample_flow_backward")
-    a = _up_args(flow, mask, "upsample_flow_backward", grad_out=g)
-    if tuple(g.shape) != (a.N, 2, 8 * a.H, 8 * a.W):
-        raise _lib.MpiFlowHipError("upsample_flow_backward: grad_out must be %s (got shape %s)" % ([a.N, 2, 8 * a.H, 8 * a.W], tuple(g.shape)))
     gf, gm = torch.empty_like(flow), torch.empty_like(mask)
     ws = _up_workspace(lib, a, 1, flow.device)
     a.out, a.grad_flow, a.grad_mask = g.data_ptr(), gf.data_ptr(), gm.data_ptr()
@@ -989,8 +904,8 @@ def flow_loss_term(flow, mask, flow_gt, valid, max_flow=400, metrics=False):
     """mpf_flow_loss_term: (v * |upsample_flow(flow, mask) - flow_gt|).mean() as a 0-d device tensor without forming the prediction;
     v = (valid >= 0.5) & (|flow_gt| < max_flow).  flow_gt [N,2,8H,8W], valid [N,8H,8W].  With metrics=True also a float64 device tensor of five
     accumulators of this prediction: sum of epe over v, counts of epe < 1, < 3, < 5, count of v.  -> (term, accumulators or None).  Asynchronous."""
-    lib = _lib.load()
     a = _up_loss_args(flow, mask, flow_gt, valid, max_flow, "flow_loss_term")
+    lib = _lib.load()
     term = torch.empty((), dtype=_f32, device=flow.device)
     acc = torch.empty(5, dtype=torch.float64, device=flow.device) if metrics else None
     ws = _up_workspace(lib, a, 0, flow.device)
@@ -1004,9 +919,9 @@ def flow_loss_term(flow, mask, flow_gt, valid, max_flow=400, metrics=False):
 def flow_loss_term_backward(flow, mask, flow_gt, valid, g, max_flow=400):
     """mpf_flow_loss_term_backward: g, a float32 scalar ON THE DEVICE (the gradient reaching the term; the kernel reads it, the host does not)
     -> (grad_flow, grad_mask) of flow_loss_term.  Bit-identical from run to run.  Asynchronous on the current stream."""
-    lib = _lib.load()
-    g = _up_tensor(g, "g", (), "flow_loss_term_backward")
+    g = check_tensor(g, "g", "flow_loss_term_backward", ())
     a = _up_loss_args(flow, mask, flow_gt, valid, max_flow, "flow_loss_term_backward", g=g)
+    lib = _lib.load()
     gf, gm = torch.empty_like(flow), torch.empty_like(mask)
     ws = _up_workspace(lib, a, 1, flow.device)
     a.g, a.grad_flow, a.grad_mask = g.data_ptr(), gf.data_ptr(), gm.data_ptr()
@@ -1015,25 +930,9 @@ def flow_loss_term_backward(flow, mask, flow_gt, valid, g, max_flow=400):
     return gf, gm
 
 
-def _gru_tensor(t, name, who, shape=None, on_gpu=True):
-    """The GRU kernels take their tensors as they are: no silent copy, cast or move.  on_gpu=False leaves the device to the caller, who checks
-    it after every tensor's own checks so that a wrong dtype or shape is named as such on any device."""
-    if not isinstance(t, torch.Tensor):
-        raise _lib.MpiFlowHipError("%s: %s must be a torch.Tensor (got %s)" % (who, name, type(t).__name__))
-    if t.dtype != _f32:
-        hint = "; call .float() on it (a half-precision kernel does not exist)" if t.dtype in (torch.float16, torch.bfloat16) else ""
-        raise _lib.MpiFlowHipError("%s: %s must be float32 (got %s)%s" % (who, name, t.dtype, hint))
-    if t.dim() != 4 or (shape is not None and any(s is not None and s != d for s, d in zip(shape, t.shape))):
-        raise _lib.MpiFlowHipError("%s: %s must be %s (got shape %s)" % (who, name, list(shape) if shape else "[B,C,H,W]", tuple(t.shape)))
-    if not t.is_contiguous():
-        raise _lib.MpiFlowHipError("%s: %s must be contiguous" % (who, name))
-    if on_gpu and not t.is_cuda:
-        raise _lib.MpiFlowHipError("%s: %s must live on the GPU (got %s); mpiflow_amd has no CPU path" % (who, name, t.device))
-    return t
-
-
-def _gru_slices(dst, terms, name, who, h, limit):
-    """terms: (tensor [B,channels,H,W], channel offset) pairs or None (absent) -> fills the MpfGruTerm array `dst`, returns the count"""
+def _gru_slices(dst, terms, name, who, h, limit, tensors):
+    """terms: (tensor [B,channels,H,W], channel offset) pairs or None (absent) -> fills the MpfGruTerm array `dst`, adds the tensors by name
+    to `tensors` (for the device check that ends the call), returns the count"""
     terms = list(terms)
     if not 1 <= len(terms) <= limit:
         raise _lib.MpiFlowHipError("%s: %s takes 1..%d slices (got %d)" % (who, name, limit, len(terms)))
@@ -1042,9 +941,7 @@ def _gru_slices(dst, terms, name, who, h, limit):
         if term is None:
             continue
         t, off = term
-        t = _gru_tensor(t, "%s[%d]" % (name, k), who, (B, None, H, W))
-        if t.device != h.device:
-            raise _lib.MpiFlowHipError("%s: %s[%d] on %s must share h's device %s" % (who, name, k, t.device, h.device))
+        t = tensors["%s[%d]" % (name, k)] = check_tensor(t, "%s[%d]" % (name, k), who, (B, None, H, W))
         if off < 0 or off + C > t.shape[1]:
             raise _lib.MpiFlowHipError("%s: %s[%d]: channels [%d, %d) are not inside its %d channels" % (who, name, k, off, off + C, t.shape[1]))
         dst[k].p, dst[k].channels, dst[k].offset = t.data_ptr(), t.shape[1], int(off)
@@ -1052,36 +949,39 @@ def _gru_slices(dst, terms, name, who, h, limit):
 
 
 def _gru_args(h, who):
-    h = _gru_tensor(h, "h", who)
+    """(MpfGruArgs, {name: tensor} of the call so far)"""
+    h = check_tensor(h, "h", who, 4, "[B,C,H,W]")
     a = _lib.MpfGruArgs()
     a.h = h.data_ptr()
     a.B, a.C, a.H, a.W = h.shape
-    return a
+    return a, dict(h=h)
 
 
 @_on_device
 def gru_reset(h, r_terms):
     """mpf_gru_reset: rh = sigmoid(sum of r_terms) * h.  h [B,C,H,W]; a term is (tensor [B,channels,H,W], channel offset) - the slice
     [offset, offset + C) read in place - or None.  float32, contiguous, on the GPU, or MpiFlowHipError.  Asynchronous on the current stream."""
-    lib = _lib.load()
-    a = _gru_args(h, "gru_reset")
-    a.nr = _gru_slices(a.r, r_terms, "r_terms", "gru_reset", h, _lib.GRU_MAX_TERMS)
+    who = "gru_reset"
+    a, tensors = _gru_args(h, who)
+    a.nr = _gru_slices(a.r, r_terms, "r_terms", who, h, _lib.GRU_MAX_TERMS, tensors)
+    check_devices(who, tensors)
     out = torch.empty_like(h)
     a.out = out.data_ptr()
-    _lib.check(lib.mpf_gru_reset(ctypes.byref(a), _stream()), "mpf_gru_reset")
+    _lib.check(_lib.load().mpf_gru_reset(ctypes.byref(a), _stream()), "mpf_gru_reset")
     return out
 
 
 @_on_device
 def gru_update(h, z_terms, q_terms):
     """mpf_gru_update: h' = (1 - z) * h + z * q with z = sigmoid(sum of z_terms), q = tanh(sum of q_terms); terms as in gru_reset."""
-    lib = _lib.load()
-    a = _gru_args(h, "gru_update")
-    a.nz = _gru_slices(a.z, z_terms, "z_terms", "gru_update", h, _lib.GRU_MAX_TERMS)
-    a.nq = _gru_slices(a.q, q_terms, "q_terms", "gru_update", h, _lib.GRU_MAX_TERMS)
+    who = "gru_update"
+    a, tensors = _gru_args(h, who)
+    a.nz = _gru_slices(a.z, z_terms, "z_terms", who, h, _lib.GRU_MAX_TERMS, tensors)
+    a.nq = _gru_slices(a.q, q_terms, "q_terms", who, h, _lib.GRU_MAX_TERMS, tensors)
+    check_devices(who, tensors)
     out = torch.empty_like(h)
     a.out = out.data_ptr()
-    _lib.check(lib.mpf_gru_update(ctypes.byref(a), _stream()), "mpf_gru_update")
+    _lib.check(_lib.load().mpf_gru_update(ctypes.byref(a), _stream()), "mpf_gru_update")
     return out
 
 
@@ -1089,17 +989,17 @@ def gru_update(h, z_terms, q_terms):
 def gru_update_backward(grad_out, h, z_terms, q_terms, dz, dq):
     """mpf_gru_update_backward: the cotangent grad_out of gru_update's h' -> d h = grad_out * (1 - z), returned; d pre_z and d pre_q are WRITTEN
     into the slices dz and dq: one or two (tensor, channel offset) destinations each.  z and q are recomputed from the terms."""
-    lib = _lib.load()
     who = "gru_update_backward"
-    a = _gru_args(h, who)
-    g = _gru_tensor(grad_out, "grad_out", who, tuple(h.shape))
-    a.nz = _gru_slices(a.z, z_terms, "z_terms", who, h, _lib.GRU_MAX_TERMS)
-    a.nq = _gru_slices(a.q, q_terms, "q_terms", who, h, _lib.GRU_MAX_TERMS)
-    _gru_slices(a.dz, dz, "dz", who, h, 2)
-    _gru_slices(a.dq, dq, "dq", who, h, 2)
+    a, tensors = _gru_args(h, who)
+    g = tensors["grad_out"] = check_tensor(grad_out, "grad_out", who, tuple(h.shape))
+    a.nz = _gru_slices(a.z, z_terms, "z_terms", who, h, _lib.GRU_MAX_TERMS, tensors)
+    a.nq = _gru_slices(a.q, q_terms, "q_terms", who, h, _lib.GRU_MAX_TERMS, tensors)
+    _gru_slices(a.dz, dz, "dz", who, h, 2, tensors)
+    _gru_slices(a.dq, dq, "dq", who, h, 2, tensors)
+    check_devices(who, tensors)
     dh = torch.empty_like(h)
     a.g, a.dh = g.data_ptr(), dh.data_ptr()
-    _lib.check(lib.mpf_gru_update_backward(ctypes.byref(a), _stream()), "mpf_gru_update_backward")
+    _lib.check(_lib.load().mpf_gru_update_backward(ctypes.byref(a), _stream()), "mpf_gru_update_backward")
     return dh
 
 
@@ -1107,16 +1007,18 @@ def gru_update_backward(grad_out, h, z_terms, q_terms, dz, dq):
 def gru_reset_backward(grad_out, h, r_terms, dr, dh=None):
     """mpf_gru_reset_backward: the cotangent grad_out of gru_reset's rh -> d pre_r WRITTEN into the slices dr (one or two destinations);
     d h = grad_out * r is ADDED into `dh` when one is given, otherwise written to a fresh tensor.  Returns dh."""
-    lib = _lib.load()
     who = "gru_reset_backward"
-    a = _gru_args(h, who)
-    g = _gru_tensor(grad_out, "grad_out", who, tuple(h.shape))
-    a.nr = _gru_slices(a.r, r_terms, "r_terms", who, h, _lib.GRU_MAX_TERMS)
-    _gru_slices(a.dr, dr, "dr", who, h, 2)
+    a, tensors = _gru_args(h, who)
+    g = tensors["grad_out"] = check_tensor(grad_out, "grad_out", who, tuple(h.shape))
+    a.nr = _gru_slices(a.r, r_terms, "r_terms", who, h, _lib.GRU_MAX_TERMS, tensors)
+    _gru_slices(a.dr, dr, "dr", who, h, 2, tensors)
     a.accumulate = int(dh is not None)
-    dh = torch.empty_like(h) if dh is None else _gru_tensor(dh, "dh", who, tuple(h.shape))
+    if dh is not None:
+        tensors["dh"] = check_tensor(dh, "dh", who, tuple(h.shape))
+    check_devices(who, tensors)
+    dh = torch.empty_like(h) if dh is None else dh
     a.g, a.dh = g.data_ptr(), dh.data_ptr()
-    _lib.check(lib.mpf_gru_reset_backward(ctypes.byref(a), _stream()), "mpf_gru_reset_backward")
+    _lib.check(_lib.load().mpf_gru_reset_backward(ctypes.byref(a), _stream()), "mpf_gru_reset_backward")
     return dh
 
 
@@ -1146,12 +1048,11 @@ def norm_default_chunks(planes, hw):
     return max(1, min(-(-2048 // planes), hw // 4096, 64))
 
 
-def _norm_check(term, name, who, shape=None):
-    """a term's own checks: type, dtype, shape, mode, parameters, a single element per statistic set; the device is left to _norm_args, which
-    checks it after everything else so that a wrong dtype, shape or mode is named as such on any device"""
+def _norm_check(term, name, who, shape=4):
+    """a term's own checks: type, x, mode, parameters, more than a single element per statistic set"""
     if not isinstance(term, NormTerm):
         raise _lib.MpiFlowHipError("%s: %s must be an ops.NormTerm (got %s)" % (who, name, type(term).__name__))
-    x = _gru_tensor(term.x, name + ".x", who, shape, on_gpu=False)
+    x = check_tensor(term.x, name + ".x", who, shape)
     if term.mode not in NORM_MODES:
         raise _lib.MpiFlowHipError("%s: %s.mode must be one of %s (got %r)" % (who, name, ", ".join(sorted(NORM_MODES)), term.mode))
     N, C, H, W = x.shape
@@ -1182,30 +1083,29 @@ def _norm_fill(ct, term):
             setattr(ct, cname, None if v is None else v.data_ptr())
 
 
-def _norm_args(term, residual, who, chunks):
-    """(MpfNormArgs, y, residual term or None, residual tensor or None): everything checked, nothing allocated"""
+def _norm_args(term, residual, who, chunks, **like):
+    """(MpfNormArgs, x, residual term or None, residual tensor or None): everything checked - `like`: further tensors of term.x's shape, by
+    name - nothing allocated"""
     x = _norm_check(term, "term", who)
     N, C, H, W = x.shape
     a = _lib.MpfNormArgs()
     a.N, a.C, a.H, a.W = N, C, H, W
+    tensors = {"term.x": x}
     rt = res = None
     if isinstance(residual, NormTerm):
         rt = residual
-        rx = _norm_check(rt, "residual", who, tuple(x.shape))
-        if rx.device != x.device:
-            raise _lib.MpiFlowHipError("%s: residual.x on %s must share term.x's device %s" % (who, rx.device, x.device))
+        tensors["residual.x"] = _norm_check(rt, "residual", who, tuple(x.shape))
     elif residual is not None:
-        res = _gru_tensor(residual, "residual", who, tuple(x.shape), on_gpu=False)
-        if res.device != x.device:
-            raise _lib.MpiFlowHipError("%s: residual on %s must share term.x's device %s" % (who, res.device, x.device))
+        res = tensors["residual"] = check_tensor(residual, "residual", who, tuple(x.shape))
         a.res = res.data_ptr()
+    for name, t in like.items():
+        tensors[name] = check_tensor(t, name, who, tuple(x.shape))
     if chunks is None:
         chunks = norm_default_chunks(N * C, H * W)
     if not isinstance(chunks, int) or not 1 <= chunks <= _lib.NORM_MAX_CHUNKS:
         raise _lib.MpiFlowHipError("%s: chunks must be an integer in 1..%d (got %r)" % (who, _lib.NORM_MAX_CHUNKS, chunks))
     a.chunks = chunks
-    if not x.is_cuda:
-        raise _lib.MpiFlowHipError("%s: term.x must live on the GPU (got %s); mpiflow_amd has no CPU path" % (who, x.device))
+    check_devices(who, tensors)
     return a, x, rt, res
 
 
@@ -1213,12 +1113,12 @@ def _norm_args(term, residual, who, chunks):
 def norm_stats(x, mode, groups=1, chunks=None):
     """mpf_norm_stats: float64 partials [N,C,chunks,2] = (mean, centred sum of squares) of every chunk of every plane of x, for a mode with statistics
     ('instance', 'batch_train', 'group').  chunks=None: norm_default_chunks.  Hand it to NormTerm(partials=...); norm_act then uses its chunks."""
-    lib = _lib.load()
     who = "norm_stats"
     if mode in NORM_MODES and mode not in _NORM_STATS:
         raise _lib.MpiFlowHipError("%s: mode '%s' has no statistics to compute" % (who, mode))
     term = NormTerm(x, mode, groups=groups)
     a, x, _, _ = _norm_args(term, None, who, chunks)
+    lib = _lib.load()
     term.partials = torch.empty((x.shape[0], x.shape[1], a.chunks, 2), dtype=torch.float64, device=x.device)
     _norm_fill(a.y, term)
     _lib.check(lib.mpf_norm_stats(ctypes.byref(a), _stream()), "mpf_norm_stats")
@@ -1240,7 +1140,6 @@ def norm_act(term, residual=None, chunks=None):
 
 @_on_device
 def _norm_act(device, term, residual, chunks):
-    lib = _lib.load()
     who = "norm_act"
     given = [t.partials for t in (term, residual) if isinstance(t, NormTerm) and t.mode in _NORM_STATS and t.partials is not None]
     if given:
@@ -1248,6 +1147,7 @@ def _norm_act(device, term, residual, chunks):
             raise _lib.MpiFlowHipError("%s: chunks=%r but the partials handed in were computed with %d" % (who, chunks, given[0].shape[2]))
         chunks = int(given[0].shape[2])
     a, x, rt, res = _norm_args(term, residual, who, chunks)
+    lib = _lib.load()
     N, C = x.shape[:2]
     fresh = []
     for t in (term, rt):
@@ -1290,14 +1190,14 @@ def norm_act_backward(grad_out, term, residual=None, chunks=None, dres=None, par
 
 @_on_device
 def _norm_act_backward(device, grad_out, term, residual, chunks, dres, param_grads):
-    lib = _lib.load()
     who = "norm_act_backward"
-    a, x, rt, res = _norm_args(term, residual, who, chunks)
-    g = _gru_tensor(grad_out, "grad_out", who, tuple(x.shape))
-    if g.device != x.device:
-        raise _lib.MpiFlowHipError("%s: grad_out on %s must share term.x's device %s" % (who, g.device, x.device))
+    like = dict(grad_out=grad_out)
+    if dres is not None and residual is not None and not isinstance(residual, NormTerm):
+        like["dres"] = dres
+    a, x, rt, res = _norm_args(term, residual, who, chunks, **like)
+    lib = _lib.load()
     N, C = x.shape[:2]
-    a.g = g.data_ptr()
+    a.g = grad_out.data_ptr()
     keep, results = [], []
     for t, ct in ((term, a.y), (rt, a.r)):
         if t is None:
@@ -1317,7 +1217,7 @@ def _norm_act_backward(device, grad_out, term, residual, chunks, dres, param_gra
         results.append((dx, dw, db))
     if res is not None:
         a.accumulate = int(dres is not None)
-        dres = torch.empty_like(x) if dres is None else _gru_tensor(dres, "dres", who, tuple(x.shape))
+        dres = torch.empty_like(x) if dres is None else dres
         a.dres = dres.data_ptr()
     if keep:
         _lib.check(lib.mpf_norm_act_backward_reduce(ctypes.byref(a), _stream()), "mpf_norm_act_backward_reduce")

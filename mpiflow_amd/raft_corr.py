@@ -17,13 +17,15 @@ them, as RAFT detaches coords1 before every lookup (RAFT/core/raft.py:123) and u
 What differs from upstream: one launch for all levels instead of one per level plus two permutes per level and lookup; gradients are wired
 (upstream's AlternateCorrBlock calls the extension's forward outside autograd: it is inference-only); coordinates may hold any value - NaN,
 +-inf and far-out values give exactly 0 and no gradient; levels smaller than 2 x 2 (H or W < 2^num_levels) are refused, where the
-reference's sampler divides by zero.  There is no CPU path and no eager fallback: MpiFlowHipError.
+reference's sampler divides by zero.  Tensors are held to the contract of _tensors.py (the device is judged last): nothing
+runs on the CPU and there is no eager fallback: MpiFlowHipError.
 """
 import torch
 import torch.nn.functional as F
 
 from . import ops
-from ._lib import CORR_MAX_LEVELS, MpiFlowHipError
+from ._lib import MpiFlowHipError
+from ._tensors import check_devices, check_pyramid, check_tensor
 
 
 class _CorrLookup(torch.autograd.Function):
@@ -42,15 +44,14 @@ class _CorrLookup(torch.autograd.Function):
         return (None, None, g1) + tuple(g2)
 
 
-def _check_map(t, name):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise MpiFlowHipError("AlternateCorrBlock: %s must be a tensor on the GPU (got %s); mpiflow_amd has no CPU path"
-                              % (name, t.device if isinstance(t, torch.Tensor) else type(t).__name__))
-    if t.dtype != torch.float32:
-        raise MpiFlowHipError("AlternateCorrBlock: %s must be float32 (got %s)" % (name, t.dtype))
-    if t.dim() != 4 or not t.is_contiguous():
-        raise MpiFlowHipError("AlternateCorrBlock: %s must be a contiguous [B,C,H,W] tensor (got shape %s, contiguous %s)"
-                              % (name, tuple(t.shape), t.is_contiguous()))
+def _check_maps(who, fmap1, fmap2, num_levels, radius):
+    """what both blocks ask of their maps (the contract of _tensors), except the device, which the block judges last: -> (B, C, H, W)"""
+    for t, name in ((fmap1, "fmap1"), (fmap2, "fmap2")):
+        check_tensor(t, name, who, 4, "[B,C,H,W]")
+    if fmap1.shape != fmap2.shape:
+        raise MpiFlowHipError("%s: fmap1 %s and fmap2 %s must agree" % (who, tuple(fmap1.shape), tuple(fmap2.shape)))
+    check_pyramid(who, fmap1.shape[2], fmap1.shape[3], num_levels, radius)
+    return fmap1.shape
 
 
 class AlternateCorrBlock:
@@ -60,21 +61,10 @@ class AlternateCorrBlock:
     RAFT/core/raft.py:104-107 unchanged.  No gradient flows to coords (None)."""
 
     def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
-        _check_map(fmap1, "fmap1")
-        _check_map(fmap2, "fmap2")
-        if fmap1.shape != fmap2.shape or fmap1.device != fmap2.device:
-            raise MpiFlowHipError("AlternateCorrBlock: fmap1 %s on %s and fmap2 %s on %s must agree"
-                                  % (tuple(fmap1.shape), fmap1.device, tuple(fmap2.shape), fmap2.device))
-        B, C, H, W = fmap1.shape
-        if not 1 <= int(num_levels) <= CORR_MAX_LEVELS:
-            raise MpiFlowHipError("AlternateCorrBlock: num_levels must be 1..%d (got %s)" % (CORR_MAX_LEVELS, num_levels))
-        if not 1 <= int(radius) <= 8:
-            raise MpiFlowHipError("AlternateCorrBlock: radius must be 1..8 (got %s)" % (radius,))
+        B, C, H, W = _check_maps("AlternateCorrBlock", fmap1, fmap2, num_levels, radius)
         if C < 32 or C % 32:
             raise MpiFlowHipError("AlternateCorrBlock: C must be a multiple of 32 (got %d)" % C)
-        if min(H, W) < 2 ** int(num_levels):
-            raise MpiFlowHipError("AlternateCorrBlock: H, W = %d, %d must be at least 2^num_levels = %d (every level at least 2 x 2)"
-                                  % (H, W, 2 ** int(num_levels)))
+        check_devices("AlternateCorrBlock", dict(fmap1=fmap1, fmap2=fmap2))
         self.num_levels, self.radius = int(num_levels), int(radius)
         # the layout change happens here, once per pair, not per lookup; autograd carries the levels' gradients back through avg_pool2d
         self.fmap1_nhwc = fmap1.permute(0, 2, 3, 1).contiguous()
@@ -161,27 +151,8 @@ class CorrBlock:
     into the same buffer).  A backward pass that reaches some lookups but not fmap1 / fmap2 leaves the buffer allocated until the block dies."""
 
     def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
-        for t, name in ((fmap1, "fmap1"), (fmap2, "fmap2")):
-            if not isinstance(t, torch.Tensor):
-                raise MpiFlowHipError("CorrBlock: %s must be a tensor (got %s)" % (name, type(t).__name__))
-            if t.dtype != torch.float32:
-                raise MpiFlowHipError("CorrBlock: %s must be float32 (got %s)" % (name, t.dtype))
-            if t.dim() != 4 or not t.is_contiguous():
-                raise MpiFlowHipError("CorrBlock: %s must be a contiguous [B,C,H,W] tensor (got shape %s, contiguous %s)"
-                                      % (name, tuple(t.shape), t.is_contiguous()))
-        if fmap1.shape != fmap2.shape or fmap1.device != fmap2.device:
-            raise MpiFlowHipError("CorrBlock: fmap1 %s on %s and fmap2 %s on %s must agree"
-                                  % (tuple(fmap1.shape), fmap1.device, tuple(fmap2.shape), fmap2.device))
-        B, C, H, W = fmap1.shape
-        if not 1 <= int(num_levels) <= CORR_MAX_LEVELS:
-            raise MpiFlowHipError("CorrBlock: num_levels must be 1..%d (got %s)" % (CORR_MAX_LEVELS, num_levels))
-        if not 1 <= int(radius) <= 8:
-            raise MpiFlowHipError("CorrBlock: radius must be 1..8 (got %s)" % (radius,))
-        if min(H, W) < 2 ** int(num_levels):
-            raise MpiFlowHipError("CorrBlock: H, W = %d, %d must be at least 2^num_levels = %d (every level at least 2 x 2)"
-                                  % (H, W, 2 ** int(num_levels)))
-        if not fmap1.is_cuda:
-            raise MpiFlowHipError("CorrBlock: fmap1 and fmap2 must be on the GPU (got %s); mpiflow_amd has no CPU path" % fmap1.device)
+        _check_maps("CorrBlock", fmap1, fmap2, num_levels, radius)
+        check_devices("CorrBlock", dict(fmap1=fmap1, fmap2=fmap2))
         self.num_levels, self.radius = int(num_levels), int(radius)
         self._shared = _GradPyramid()
         self.corr_pyramid = list(_CorrPyramid.apply(self._shared, self.num_levels, fmap1, fmap2))

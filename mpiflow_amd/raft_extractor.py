@@ -20,9 +20,10 @@ convolutions are torch's (MIOpen), and so is Dropout2d.
 The gradient of an identity shortcut is written to a tensor of its own and added to the first convolution's input gradient by autograd
 (ops.norm_act_backward can add into a given buffer, but that gradient does not exist yet when the block's tail runs its backward).
 
-Limits: float32 only (anything else is refused with a message that says to call `.float()`), tensors on the GPU; non-contiguous input is made
-contiguous.  A training-mode instance or batch norm over a single value per statistic set is refused, as torch refuses it.  There is no CPU
-path and no eager fallback: MpiFlowHipError.  Double backward is refused.
+Limits: inputs are held to the contract of _tensors.py: float32 only (the refusal says to call `.float()`), on the GPU, the
+device judged last - with one difference: non-contiguous input is made contiguous, not refused.  A training-mode instance or
+batch norm over a single value per statistic set is refused, as torch refuses it.  Nothing runs on the CPU and there is no eager fallback:
+MpiFlowHipError.  Double backward is refused.
 """
 import torch
 import torch.nn as nn
@@ -30,6 +31,7 @@ from torch.autograd.function import once_differentiable
 
 from . import ops
 from ._lib import MpiFlowHipError
+from ._tensors import check_devices, check_tensor
 
 NORM_FNS = ("group", "batch", "instance", "none")
 
@@ -57,12 +59,16 @@ def _mode(norm):
     return "none"
 
 
-def _term(x, norm):
-    mode = _mode(norm)
+def _term(x, norm, mode=None, mean=None, rstd=None):
+    """the kernel's term for x and its holder module; backward passes the mode the forward pass saw, not the holder's present state, and the
+    statistics that pass saved"""
+    mode = _mode(norm) if mode is None else mode
     if mode == "none":
         return ops.NormTerm(x, "none")
-    return ops.NormTerm(x, mode, weight=getattr(norm, "weight", None), bias=getattr(norm, "bias", None), groups=getattr(norm, "num_groups", 1),
+    term = ops.NormTerm(x, mode, weight=getattr(norm, "weight", None), bias=getattr(norm, "bias", None), groups=getattr(norm, "num_groups", 1),
                         running_mean=norm.running_mean if mode == "batch_eval" else None, running_var=norm.running_var if mode == "batch_eval" else None)
+    term.mean, term.rstd = mean, rstd
+    return term
 
 
 def _update_running(norm, term, count):
@@ -102,16 +108,8 @@ class _NormAct(torch.autograd.Function):
     def backward(ctx, grad_out):
         x, res, rx, mean, rstd, rmean, rrstd = ctx.saved_tensors
         norm, rnorm, mode, rmode = ctx.holders
-
-        def rebuild(t, holder, m, mu, rs):
-            term = ops.NormTerm(t, m, weight=getattr(holder, "weight", None) if m != "none" else None,
-                                bias=getattr(holder, "bias", None) if m != "none" else None, groups=getattr(holder, "num_groups", 1),
-                                running_mean=holder.running_mean if m == "batch_eval" else None, running_var=holder.running_var if m == "batch_eval" else None)
-            term.mean, term.rstd = mu, rs
-            return term
-
-        term = rebuild(x, norm, mode, mean, rstd)
-        residual = rebuild(rx, rnorm, rmode, rmean, rrstd) if rx is not None else res
+        term = _term(x, norm, mode, mean, rstd)
+        residual = _term(rx, rnorm, rmode, rmean, rrstd) if rx is not None else res
         needs = ctx.needs_input_grad
         dx, dw, db, dr = ops.norm_act_backward(grad_out.contiguous(), term, residual, param_grads=any(needs[3:5]) or any(needs[7:9]))
         drx = drw = drb = dres = None
@@ -129,21 +127,9 @@ def _fused(x, norm, res=None, rx=None, rnorm=None):
     return _NormAct.apply(norm, rnorm, x, p(norm, "weight"), p(norm, "bias"), res, rx, p(rnorm, "weight"), p(rnorm, "bias"))
 
 
-def _image(x, name, who):
-    """type, dtype and shape of a module input, then the device; contiguous on return"""
-    if not isinstance(x, torch.Tensor):
-        raise MpiFlowHipError("%s: %s must be a torch.Tensor (got %s)" % (who, name, type(x).__name__))
-    if x.dtype != torch.float32:
-        raise MpiFlowHipError("%s: %s must be float32 (got %s); call .float() on it (the norm kernels are float32 only)" % (who, name, x.dtype))
-    if x.dim() != 4:
-        raise MpiFlowHipError("%s: %s must be [N,C,H,W] (got shape %s)" % (who, name, tuple(x.shape)))
-    return x
-
-
-def _on_gpu(x, name, who):
-    if not x.is_cuda:
-        raise MpiFlowHipError("%s: %s must live on the GPU (got %s); mpiflow_amd has no CPU path" % (who, name, x.device))
-    return x.contiguous()
+def _contiguous(x):
+    """a module input is made contiguous where it is not (the module docstring promises it); the contract of _tensors only checks"""
+    return x.contiguous() if isinstance(x, torch.Tensor) else x
 
 
 def _conv_out(size, conv, axis):
@@ -179,11 +165,12 @@ class _Block(nn.Module):
 
     def _check(self, x):
         who = type(self).__name__
-        x = _image(x, "x", who)
+        x = check_tensor(_contiguous(x), "x", who, 4, "[N,C,H,W]")
         if x.shape[1] != self.conv1.in_channels:
             raise MpiFlowHipError("%s: x must have %d channels (got shape %s)" % (who, self.conv1.in_channels, tuple(x.shape)))
         self._walk(x.shape[0], x.shape[2], x.shape[3], who)
-        return _on_gpu(x, "x", who)
+        check_devices(who, dict(x=x))
+        return x
 
 
 class ResidualBlock(_Block):
@@ -271,13 +258,13 @@ class _Encoder(nn.Module):
         if is_list:
             if len(x) != 2:
                 raise MpiFlowHipError("%s: a list input must hold two image batches (got %d)" % (who, len(x)))
-            x = [_image(t, "x[%d]" % k, who) for k, t in enumerate(x)]
+            x = [check_tensor(_contiguous(t), "x[%d]" % k, who, 4, "[N,C,H,W]") for k, t in enumerate(x)]
             if x[0].shape != x[1].shape or x[0].device != x[1].device:
                 raise MpiFlowHipError("%s: the two image batches must share shape and device (got %s on %s, %s on %s)"
                                       % (who, tuple(x[0].shape), x[0].device, tuple(x[1].shape), x[1].device))
             batch_dim = x[0].shape[0]
             x = torch.cat(x, dim=0)
-        x = _image(x, "x", who)
+        x = check_tensor(_contiguous(x), "x", who, 4, "[N,C,H,W]")
         if x.shape[1] != 3:
             raise MpiFlowHipError("%s: x must have 3 channels (got shape %s)" % (who, tuple(x.shape)))
         N, H, W = x.shape[0], _conv_out(x.shape[2], self.conv1, 0), _conv_out(x.shape[3], self.conv1, 1)
@@ -285,7 +272,7 @@ class _Encoder(nn.Module):
         for layer in (self.layer1, self.layer2, self.layer3):
             for blk in layer:
                 H, W = blk._walk(N, H, W, who)
-        x = _on_gpu(x, "x", who)
+        check_devices(who, dict(x=x))
         x = _fused(self.conv1(x), self.norm1)
         x = self.layer3(self.layer2(self.layer1(x)))
         x = self.conv2(x)

@@ -21,9 +21,9 @@ the two convolution outputs (the shared-buffer pattern of raft_corr.CorrBlock): 
 inp does not change over the iterations: `context(inp)` computes its share of all gate convolutions once, and a call with `context=` convolves
 only the motion features.  Results equal upstream's up to fp32 summation order.  The convolutions themselves are torch's (MIOpen).
 
-Limits: float32 only (a half-precision tensor is refused with a message that says to call `.float()`), contiguous NCHW tensors on the GPU;
-there is no CPU path and no eager fallback: MpiFlowHipError.  Double backward is refused.  torch.autograd.grad with respect to the GRU's
-internal convolution outputs is not supported (their gradients travel in the shared buffers).
+Limits: tensors are held to the contract of _tensors.py: float32 only (the refusal says to call `.float()`), contiguous NCHW,
+on the GPU, the device judged last; nothing runs on the CPU and there is no eager fallback: MpiFlowHipError.  Double backward is refused.
+torch.autograd.grad with respect to the GRU's internal convolution outputs is not supported (their gradients travel in the shared buffers).
 """
 import weakref
 
@@ -34,6 +34,7 @@ from torch.autograd.function import once_differentiable
 
 from . import ops
 from ._lib import MpiFlowHipError
+from ._tensors import check_devices, check_tensor
 
 
 class _HalfGrads:
@@ -96,21 +97,6 @@ class _Reset(torch.autograd.Function):
         return None, dh, g2, g3, (g3 if cx is not None else None)
 
 
-def _check(t, name, who, shape):
-    """type, dtype, shape, contiguity; the device comes last (_on_gpu), so that a wrong dtype or shape is named as such on any device"""
-    return ops._gru_tensor(t, name, who, shape, on_gpu=False)
-
-
-def _on_gpu(who, **tensors):
-    first = None
-    for name, t in tensors.items():
-        if not t.is_cuda:
-            raise MpiFlowHipError("%s: %s must live on the GPU (got %s); mpiflow_amd has no CPU path" % (who, name, t.device))
-        first = t.device if first is None else first
-        if t.device != first:
-            raise MpiFlowHipError("%s: %s on %s must share the device %s of the other tensors" % (who, name, t.device, first))
-
-
 class GruContext:
     """The iteration-invariant part of a GRU's gate convolutions for one `inp` (from `context(inp)`): per half the [B,3C,H,W] sum-term (z|r|q,
     biases included) and the weights packed for the rest of the input.  Differentiable: its gradient accumulates over the calls that use it."""
@@ -149,11 +135,11 @@ class _SplitGRU(nn.Module):
         """The share of `inp` - the FIRST inp.shape[1] channels of the GRU's input x = cat([inp, rest]) - in all gate convolutions of both halves,
         biases included.  Compute it once per forward pass and pass it to every call as `context=`."""
         who = type(self).__name__ + ".context"
-        inp = _check(inp, "inp", who, None)
+        inp = check_tensor(inp, "inp", who, 4, "[B,C,H,W]")
         n_ctx = inp.shape[1]
         if not 1 <= n_ctx < self.input_dim:
             raise MpiFlowHipError("%s: inp must have 1..%d channels, fewer than input_dim (got shape %s)" % (who, self.input_dim - 1, tuple(inp.shape)))
-        _on_gpu(who, inp=inp)
+        check_devices(who, dict(inp=inp))
         packed = self._pack(n_ctx)
         terms = [F.conv2d(inp, p[0], p[1], padding=half[2]) for p, half in zip(packed, self.HALVES)]
         return GruContext(terms, packed, n_ctx, (inp.shape[0], inp.shape[2], inp.shape[3]))
@@ -162,7 +148,7 @@ class _SplitGRU(nn.Module):
         """h [B,hidden_dim,H,W], x [B,input_dim,H,W] -> h'.  With `context=self.context(inp)`, x is the REST of the input: the
         input_dim - inp.shape[1] channels that follow inp in upstream's cat([inp, motion_features])."""
         who = type(self).__name__
-        h = _check(h, "h", who, (None, self.hidden_dim, None, None))
+        h = check_tensor(h, "h", who, (None, self.hidden_dim, None, None))
         B, C, H, W = h.shape
         if context is None:
             n_x, packed, terms = self.input_dim, self._pack(0), [None] * len(self.HALVES)
@@ -172,8 +158,8 @@ class _SplitGRU(nn.Module):
             if context.shape != (B, H, W):
                 raise MpiFlowHipError("%s: context was computed for [B,H,W] = %s, h is %s" % (who, list(context.shape), tuple(h.shape)))
             n_x, packed, terms = self.input_dim - context.channels, context.packed, context.terms
-        x = _check(x, "x", who, (B, n_x, H, W))
-        _on_gpu(who, h=h, x=x, **({} if context is None else {"context": terms[0]}))
+        x = check_tensor(x, "x", who, (B, n_x, H, W))
+        check_devices(who, dict(h=h, x=x, **({} if context is None else {"context": terms[0]})))
         for (_, bias, w_x, w_h, w_q), cx, (_, _, pad) in zip(packed, terms, self.HALVES):
             shared = _HalfGrads()
             xg = F.conv2d(x, w_x, bias if cx is None else None, padding=pad)

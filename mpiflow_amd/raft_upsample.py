@@ -16,7 +16,7 @@ backward pass recomputes it.  Each prediction is ONE autograd node that saves on
 What differs from upstream: `sequence_loss` takes (flows, masks) instead of the upsampled predictions; its sums are folded in fp64 in a fixed
 order (upstream: torch's fp32 mean), so results are bit-identical from run to run; the four metrics cost one device-to-host copy of five
 numbers instead of four `.item()` calls.  float32 only: a half-precision mask (what --mixed_precision hands over) is refused with a message
-that says to call `.float()`.  There is no CPU path and no eager fallback: MpiFlowHipError.
+that says to call `.float()`.  Tensors are held to the contract of _tensors.py: no eager fallback, MpiFlowHipError.
 """
 import torch
 
