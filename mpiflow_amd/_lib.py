@@ -258,13 +258,18 @@ class MpiFlowHipError(RuntimeError):
     pass
 
 
-def _bind(path):
+def _bind(path, missing_ok=False):
+    """dlopen + set every signature of SIGNATURES; -> (library, names it lacks: only ever non-empty with missing_ok)"""
     lib = ctypes.CDLL(path)
+    skipped = []
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
+        if missing_ok and not hasattr(lib, name):
+            skipped.append(name)
+            continue
+        fn = getattr(lib, name)          # AttributeError here = header and library disagree
         fn.restype = res
         fn.argtypes = args
-    return lib
+    return lib, skipped
 
 
 def load_witness():
@@ -273,7 +278,7 @@ def load_witness():
     if _witness is None:
         if not os.path.exists(WITNESS_PATH):
             raise MpiFlowHipError("libmpiflow_hip_witness.so not found at %s - `make -C mpiflow_amd/csrc` builds it beside the product library" % WITNESS_PATH)
-        _witness = _bind(WITNESS_PATH)
+        _witness = _bind(WITNESS_PATH)[0]
         assert _witness.mpf_is_witness_build() == 1
     return _witness
 
@@ -310,15 +315,7 @@ def load():
         raise MpiFlowHipError(
             "libmpiflow_hip.so not found at %s - build it with `python __graft_entry__.py` or "
             "`make -C mpiflow_amd/csrc` (hipcc --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
-    lib = ctypes.CDLL(LIB_PATH)
-    skipped = []
-    for name, (res, args) in SIGNATURES.items():
-        if os.environ.get("MPIFLOW_HIP_LIB") and not hasattr(lib, name):
-            skipped.append(name)
-            continue
-        fn = getattr(lib, name)          # AttributeError here = header and library disagree
-        fn.restype = res
-        fn.argtypes = args
+    lib, skipped = _bind(LIB_PATH, missing_ok=bool(os.environ.get("MPIFLOW_HIP_LIB")))
     if skipped:                          # development hook only: say which calls will fail instead of failing late with an AttributeError
         import sys
         sys.stderr.write("mpiflow_amd: MPIFLOW_HIP_LIB=%s lacks %d symbol(s) of include/mpiflow_hip.h: %s\n" % (LIB_PATH, len(skipped), ", ".join(skipped)))

@@ -1395,6 +1395,23 @@ static MpfSupportSet mpf_support_set(const MpfWarpView *views, const MpfViewSupp
     return ss;
 }
 
+// The views of a multi-view Stage B launch, checked and copied into the kernel's argument block (n_views is in range, views is not null).
+// `who` is the entry point the messages name.
+static int view_set(const char *who, const MpfWarpView *views, int n_views, MpfViewSet &vs, bool &has_mask)
+{
+    memset(&vs, 0, sizeof(vs));
+    has_mask = views[0].d_mask_quads != nullptr;
+    for (int v = 0; v < n_views; ++v) {
+        const MpfWarpView &w = views[v];
+        MPF_REQUIRE(w.d_params && w.d_rgb, "%s: view %d: null params / rgb", who, v);
+        MPF_REQUIRE((w.d_mask_quads != nullptr) == has_mask, "%s: all views of a call take a mask, or none does", who);
+        MPF_REQUIRE((w.d_mask_quads == nullptr) == (w.d_objmask == nullptr), "%s: view %d: mask quads and objmask output go together", who, v);
+        MPF_REQUIRE(mpf_aligned16(w.d_mask_quads), "%s: view %d: mask quads must be 16-byte aligned", who, v);
+        vs.v[v] = w;
+    }
+    return 0;
+}
+
 static int warp_composite_views_impl(const float *d_rgba, int interleaved, const MpfWarpView *views, const MpfViewSupport *supports, int n_views, int S, int H,
                                      int W, void *stream)
 {
@@ -1405,16 +1422,8 @@ static int warp_composite_views_impl(const float *d_rgba, int interleaved, const
     MPF_REQUIRE((int64_t)H * W < ((int64_t)1 << 27), "mpf_warp_composite_views: H*W too large for 32-bit byte offsets");
     MPF_REQUIRE(mpf_aligned16(d_rgba), "mpf_warp_composite_views: the stack must be 16-byte aligned");
     MpfViewSet vs;
-    memset(&vs, 0, sizeof(vs));
-    const bool has_mask = views[0].d_mask_quads != nullptr;
-    for (int v = 0; v < n_views; ++v) {
-        const MpfWarpView &w = views[v];
-        MPF_REQUIRE(w.d_params && w.d_rgb, "mpf_warp_composite_views: view %d: null params / rgb", v);
-        MPF_REQUIRE((w.d_mask_quads != nullptr) == has_mask, "mpf_warp_composite_views: all views of a call take a mask, or none does");
-        MPF_REQUIRE((w.d_mask_quads == nullptr) == (w.d_objmask == nullptr), "mpf_warp_composite_views: view %d: mask quads and objmask output go together", v);
-        MPF_REQUIRE(mpf_aligned16(w.d_mask_quads), "mpf_warp_composite_views: view %d: mask quads must be 16-byte aligned", v);
-        vs.v[v] = w;
-    }
+    bool has_mask;
+    if (const int rc = view_set("mpf_warp_composite_views", views, n_views, vs, has_mask)) return rc;
     const MpfSupportSet ss = mpf_support_set(views, supports, n_views, has_mask);
 #ifdef MPF_WITNESS
     if (g_stage_b_variant == 20 && interleaved == 2 && S <= MPF_LT_MAXS) {          // the retired LDS-staged variant renders every tile
@@ -1744,22 +1753,19 @@ k_src_blend_flow(const float *__restrict__ mpi, const float *__restrict__ img, c
     mpf_sbf_body<PX, P, NL, ACT, BLEND, NT_STORE, 2>(a, S, H, W, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
+// Stage A+C with the [S,4,H,W] stack or a bare sigma tensor, as `args` says (plane_stride / sigma_off); T follows from PX here.
 template <int PX, int P>
-static int launch_sbf(const float *mpi, const float *img, const float *params, int S, int H, int W, float clip,
-                      float *rgba, float *planar, float *tacc, float *flows, uint8_t *src_u8, const float *om, float *q0, float *q1,
-                      const float *cum_mask, hipStream_t st, int64_t plane_stride = 0, int64_t sigma_off = 0, unsigned *sup = nullptr, unsigned *sup_c = nullptr,
-                      unsigned tag = 0)
+static int launch_sbf(const MpfSbfArgs &args, int S, int H, int W, hipStream_t st)
 {
-    const int64_t N = (int64_t)H * W;
-    const int64_t T = (N + PX - 1) / PX;
-    if (plane_stride == 0) { plane_stride = 4 * N; sigma_off = 3 * N; }          // the [S,4,H,W] stack
-    dim3 grid((unsigned)((T + 255) / 256)), block(256);
-    const bool blend = rgba || planar || tacc;
-#define MPF_SBF_GO(NLv, ACTv, BLv) hipLaunchKernelGGL((k_src_blend_flow<PX, P, NLv, ACTv, BLv>), grid, block, 0, st, mpi, img, params, S, H, W, clip, rgba, \
-                                              planar, tacc, flows, T, src_u8, om, reinterpret_cast<float4 *>(q0), reinterpret_cast<float4 *>(q1), cum_mask, plane_stride, sigma_off, sup, sup_c, tag)
+    MpfSbfArgs a = args;
+    a.T = ((int64_t)H * W + PX - 1) / PX;
+    dim3 grid((unsigned)((a.T + 255) / 256)), block(256);
+    const bool blend = a.out_rgba || a.out_planar || a.out_tacc;
+#define MPF_SBF_GO(NLv, ACTv, BLv) hipLaunchKernelGGL((k_src_blend_flow<PX, P, NLv, ACTv, BLv>), grid, block, 0, st, a.mpi, a.img, a.params, S, H, W, a.flow_clip, a.out_rgba, \
+                                              a.out_planar, a.out_tacc, a.flows, a.T, a.src_u8, a.obj_mask, a.quads, a.quads_c, a.cum_mask, a.plane_stride, a.sigma_off, a.sup, a.sup_c, a.tag)
 #define MPF_SBF_NL(NLv)                                                                              \
-    if (cum_mask) { if (blend) MPF_SBF_GO(NLv, true, true); else MPF_SBF_GO(NLv, true, false); }    \
-    else          { if (blend) MPF_SBF_GO(NLv, false, true); else MPF_SBF_GO(NLv, false, false); }
+    if (a.cum_mask) { if (blend) MPF_SBF_GO(NLv, true, true); else MPF_SBF_GO(NLv, true, false); }  \
+    else            { if (blend) MPF_SBF_GO(NLv, false, true); else MPF_SBF_GO(NLv, false, false); }
     if (S < 256) { MPF_SBF_NL(2) } else { MPF_SBF_NL(3) }
 #undef MPF_SBF_NL
 #undef MPF_SBF_GO
@@ -1768,31 +1774,33 @@ static int launch_sbf(const float *mpi, const float *img, const float *params, i
 
 static int g_sbf_px = 0;   // 0 = auto; tuning knob for benches (mpf_tune)
 
-static int src_blend_flow_impl(const float *d_mpi, const float *d_img, const float *d_params, int P, int S, int H, int W,
-                               float flow_clip, float *d_out_rgba, float *d_out_rgb_planar, float *d_out_tacc,
-                               float *d_flows, uint8_t *d_src_u8_bgr, const float *d_obj_mask, float *d_quads,
-                               float *d_quads_complement, const float *d_cum_mask, unsigned *d_support, unsigned *d_support_complement, unsigned tag, void *stream)
+// `in`: the Stage A+C block as the caller passed it; T, plane_stride and sigma_off are set on the way to the launch
+static int src_blend_flow_impl(const MpfSbfArgs &in, int P, int S, int H, int W, void *stream)
 {
-    MPF_REQUIRE((d_support == nullptr || d_quads) && (d_support_complement == nullptr || d_quads_complement), "mpf_src_blend_flow: a support map needs its quads");
-    MPF_REQUIRE(d_mpi && d_img && d_params, "mpf_src_blend_flow: null pointer");
-    MPF_REQUIRE((d_quads == nullptr && d_quads_complement == nullptr) || d_obj_mask, "mpf_src_blend_flow: quads need d_obj_mask");
-    MPF_REQUIRE(mpf_aligned16(d_quads) && mpf_aligned16(d_quads_complement), "mpf_src_blend_flow: quads must be 16-byte aligned");
+    MPF_REQUIRE((in.sup == nullptr || in.quads) && (in.sup_c == nullptr || in.quads_c), "mpf_src_blend_flow: a support map needs its quads");
+    MPF_REQUIRE(in.mpi && in.img && in.params, "mpf_src_blend_flow: null pointer");
+    MPF_REQUIRE((in.quads == nullptr && in.quads_c == nullptr) || in.obj_mask, "mpf_src_blend_flow: quads need d_obj_mask");
+    MPF_REQUIRE(mpf_aligned16(in.quads) && mpf_aligned16(in.quads_c), "mpf_src_blend_flow: quads must be 16-byte aligned");
     MPF_REQUIRE(P >= 0 && P <= 2, "mpf_src_blend_flow: P must be 0, 1 or 2 (got %d)", P);
-    MPF_REQUIRE((P == 0) == (d_flows == nullptr), "mpf_src_blend_flow: flows output iff P > 0");
+    MPF_REQUIRE((P == 0) == (in.flows == nullptr), "mpf_src_blend_flow: flows output iff P > 0");
     MPF_REQUIRE(S >= 1 && S < 4096 && H >= 1 && W >= 1, "mpf_src_blend_flow: bad shape S=%d H=%d W=%d", S, H, W);
-    MPF_REQUIRE(!d_out_rgba || mpf_aligned16(d_out_rgba), "mpf_src_blend_flow: rgba output must be 16-byte aligned");
+    MPF_REQUIRE(!in.out_rgba || mpf_aligned16(in.out_rgba), "mpf_src_blend_flow: rgba output must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
+    const int64_t N = (int64_t)H * W;
+    MpfSbfArgs a = in;
+    if (!a.quads && !a.quads_c) a.obj_mask = nullptr;      // the mask is read for the quads only
+    a.plane_stride = 4 * N; a.sigma_off = 3 * N;           // the [S,4,H,W] stack
     int px = g_sbf_px;
     if (px != 1 && px != 2) {
         // residency heuristic (256 CUs x 8 resident 256-thread workgroups): prefer the split that leaves no thin second round
-        const int64_t wg1 = ((int64_t)H * W + 255) / 256;
+        const int64_t wg1 = (N + 255) / 256;
         px = (wg1 > 2048 && wg1 <= 4096) ? 2 : 1;
     }
-#define MPF_SBF(PXv)                                                                                                     \
-    switch (P) {                                                                                                         \
-    case 0: return launch_sbf<PXv, 0>(d_mpi, d_img, d_params, S, H, W, flow_clip, d_out_rgba, d_out_rgb_planar, d_out_tacc, d_flows, d_src_u8_bgr, (d_quads || d_quads_complement) ? d_obj_mask : nullptr, d_quads, d_quads_complement, d_cum_mask, st, 0, 0, d_support, d_support_complement, tag); \
-    case 1: return launch_sbf<PXv, 1>(d_mpi, d_img, d_params, S, H, W, flow_clip, d_out_rgba, d_out_rgb_planar, d_out_tacc, d_flows, d_src_u8_bgr, (d_quads || d_quads_complement) ? d_obj_mask : nullptr, d_quads, d_quads_complement, d_cum_mask, st, 0, 0, d_support, d_support_complement, tag); \
-    default: return launch_sbf<PXv, 2>(d_mpi, d_img, d_params, S, H, W, flow_clip, d_out_rgba, d_out_rgb_planar, d_out_tacc, d_flows, d_src_u8_bgr, (d_quads || d_quads_complement) ? d_obj_mask : nullptr, d_quads, d_quads_complement, d_cum_mask, st, 0, 0, d_support, d_support_complement, tag); \
+#define MPF_SBF(PXv)                                      \
+    switch (P) {                                          \
+    case 0: return launch_sbf<PXv, 0>(a, S, H, W, st);    \
+    case 1: return launch_sbf<PXv, 1>(a, S, H, W, st);    \
+    default: return launch_sbf<PXv, 2>(a, S, H, W, st);   \
     }
     if (px == 2) { MPF_SBF(2) }
     MPF_SBF(1)
@@ -1804,8 +1812,9 @@ extern "C" int mpf_src_blend_flow(const float *d_mpi, const float *d_img, const 
                                   float *d_flows, uint8_t *d_src_u8_bgr, const float *d_obj_mask, float *d_quads,
                                   float *d_quads_complement, const float *d_cum_mask, void *stream)
 {
-    return src_blend_flow_impl(d_mpi, d_img, d_params, P, S, H, W, flow_clip, d_out_rgba, d_out_rgb_planar, d_out_tacc, d_flows, d_src_u8_bgr, d_obj_mask, d_quads,
-                               d_quads_complement, d_cum_mask, nullptr, nullptr, 0, stream);
+    const MpfSbfArgs a = { d_mpi, d_img, d_params, flow_clip, d_out_rgba, d_out_rgb_planar, d_out_tacc, d_flows, 0, d_src_u8_bgr, d_obj_mask,
+                           reinterpret_cast<float4 *>(d_quads), reinterpret_cast<float4 *>(d_quads_complement), d_cum_mask, 0, 0, nullptr, nullptr, 0 };
+    return src_blend_flow_impl(a, P, S, H, W, stream);
 }
 
 extern "C" int mpf_src_blend_flow_support(const float *d_mpi, const float *d_img, const float *d_params, int P, int S, int H, int W,
@@ -1814,8 +1823,9 @@ extern "C" int mpf_src_blend_flow_support(const float *d_mpi, const float *d_img
                                           float *d_quads_complement, const float *d_cum_mask, uint32_t *d_support, uint32_t *d_support_complement, uint32_t tag,
                                           void *stream)
 {
-    return src_blend_flow_impl(d_mpi, d_img, d_params, P, S, H, W, flow_clip, d_out_rgba, d_out_rgb_planar, d_out_tacc, d_flows, d_src_u8_bgr, d_obj_mask, d_quads,
-                               d_quads_complement, d_cum_mask, d_support, d_support_complement, tag, stream);
+    const MpfSbfArgs a = { d_mpi, d_img, d_params, flow_clip, d_out_rgba, d_out_rgb_planar, d_out_tacc, d_flows, 0, d_src_u8_bgr, d_obj_mask,
+                           reinterpret_cast<float4 *>(d_quads), reinterpret_cast<float4 *>(d_quads_complement), d_cum_mask, 0, 0, d_support, d_support_complement, tag };
+    return src_blend_flow_impl(a, P, S, H, W, stream);
 }
 
 // Stage D for one pixel (utils/utils.py:237-283): thresholds, layer select, uint8 BGR frame, fill mask, merged flow.  Shared by k_merge and
@@ -2120,6 +2130,100 @@ static int launch_overlap(const float *rgba_b, const MpfViewSet &vs, unsigned V,
     return mpf_launch_status("k_pair_overlap");
 }
 
+// What makes the merge folded into a pair launch (merge_prev) race-free, checked against the buffers of the launch it rides on (`next`: its Stage A+C block).
+static int merge_prev_check(const MpfMergeArgs &mg, const float *d_rgba, const MpfWarpView *views, int n_views, const MpfSbfArgs &next, int P, int S, int H, int W)
+{
+    MPF_REQUIRE(mg.d_frame && mg.d_frame_dyn && mg.d_mask && mg.d_mask_dyn && mg.d_flow && mg.d_flow_dyn && mg.d_obj_mask && mg.d_flow_mix && mg.d_frame_mix &&
+                    mg.d_fill_mask, "mpf_warp_views_blend_next_merge_prev: merge_prev has a null pointer");
+    for (int v = 0; v < n_views && views; ++v)
+        MPF_REQUIRE(views[v].d_rgb != mg.d_frame && views[v].d_rgb != mg.d_frame_dyn && views[v].d_objmask != mg.d_mask && views[v].d_objmask != mg.d_mask_dyn,
+                    "mpf_warp_views_blend_next_merge_prev: the merged pair's views must not be the views this launch renders");
+    MPF_REQUIRE(mg.obj_mask_stride >= 0 && mg.obj_mask_stride <= 4, "mpf_warp_views_blend_next_merge_prev: obj_mask_stride must be 0..4");
+    // The folded merge is race-free only if (1) the thread that merges pixel n is the ONLY one that writes anything the merge of pixel n reads:
+    // the merged pair's flows are either disjoint from the flows this launch writes or exactly those planes (d_flows_next + {0, 2N}: same pixel,
+    // same thread, read before written), its object mask is disjoint from the launch's outputs or exactly the .x of d_quads_next (same argument),
+    // and (2) what the merge writes overlaps nothing this launch reads or writes.
+    const size_t Nn = (size_t)H * W;
+    auto overlaps = [](const void *a, size_t an, const void *b, size_t bn) {
+        return a && b && (const char *)a < (const char *)b + bn && (const char *)b < (const char *)a + an;
+    };
+    const size_t flows_next_bytes = (size_t)P * 2 * Nn * sizeof(float);
+    const float *fl[2] = { mg.d_flow, mg.d_flow_dyn };
+    for (int k = 0; k < 2; ++k) {
+        const bool aligned = next.flows && P == 2 && (fl[k] == next.flows || fl[k] == next.flows + 2 * Nn);
+        MPF_REQUIRE(aligned || !overlaps(fl[k], 2 * Nn * sizeof(float), next.flows, flows_next_bytes),
+                    "mpf_warp_views_blend_next_merge_prev: merge_prev's flows must be disjoint from d_flows_next or exactly its two pose planes");
+    }
+    const size_t om_bytes = Nn * sizeof(float) * (size_t)(mg.obj_mask_stride > 1 ? mg.obj_mask_stride : 1);
+    const bool om_is_quads = mg.obj_mask_stride == 4 && (const void *)mg.d_obj_mask == (const void *)next.quads;
+    MPF_REQUIRE(om_is_quads || (!overlaps(mg.d_obj_mask, om_bytes, next.quads, Nn * 16) && !overlaps(mg.d_obj_mask, om_bytes, next.quads_c, Nn * 16) &&
+                                !overlaps(mg.d_obj_mask, om_bytes, next.out_rgba, (size_t)S * Nn * 16) && !overlaps(mg.d_obj_mask, om_bytes, next.flows, flows_next_bytes)),
+                "mpf_warp_views_blend_next_merge_prev: merge_prev's object mask must not be a buffer this launch writes (other than the .x of d_quads_next, stride 4)");
+    const struct { const void *p; size_t n; const char *what; } outs[3] = { { mg.d_flow_mix, 2 * Nn * sizeof(float), "flow_mix" }, { mg.d_frame_mix, 3 * Nn, "frame_mix" },
+                                                                              { mg.d_fill_mask, Nn, "fill_mask" } };
+    for (int k = 0; k < 3; ++k) {
+        bool bad = overlaps(outs[k].p, outs[k].n, next.out_rgba, (size_t)S * Nn * 16) || overlaps(outs[k].p, outs[k].n, d_rgba, (size_t)S * Nn * 16) ||
+                   overlaps(outs[k].p, outs[k].n, next.flows, flows_next_bytes) || overlaps(outs[k].p, outs[k].n, next.quads, Nn * 16) ||
+                   overlaps(outs[k].p, outs[k].n, next.quads_c, Nn * 16) || overlaps(outs[k].p, outs[k].n, next.src_u8, 3 * Nn) ||
+                   overlaps(outs[k].p, outs[k].n, next.obj_mask, Nn * 4) || overlaps(outs[k].p, outs[k].n, mg.d_obj_mask, om_bytes) ||
+                   overlaps(outs[k].p, outs[k].n, mg.d_flow, 2 * Nn * 4) || overlaps(outs[k].p, outs[k].n, mg.d_flow_dyn, 2 * Nn * 4) ||
+                   overlaps(outs[k].p, outs[k].n, mg.d_frame, 3 * Nn * 4) || overlaps(outs[k].p, outs[k].n, mg.d_frame_dyn, 3 * Nn * 4) ||
+                   overlaps(outs[k].p, outs[k].n, mg.d_mask, Nn * 4) || overlaps(outs[k].p, outs[k].n, mg.d_mask_dyn, Nn * 4);
+        for (int j = k + 1; j < 3; ++j) bad = bad || overlaps(outs[k].p, outs[k].n, outs[j].p, outs[j].n);
+        for (int v = 0; v < n_views && views; ++v)
+            bad = bad || overlaps(outs[k].p, outs[k].n, views[v].d_rgb, 3 * Nn * 4) || overlaps(outs[k].p, outs[k].n, views[v].d_objmask, Nn * 4) ||
+                  overlaps(outs[k].p, outs[k].n, views[v].d_depth, Nn * 4) || overlaps(outs[k].p, outs[k].n, views[v].d_tgt_mask, Nn * 4) ||
+                  overlaps(outs[k].p, outs[k].n, views[v].d_rgb_u8_bgr, 3 * Nn) || overlaps(outs[k].p, outs[k].n, views[v].d_mask_quads, Nn * 16);
+        MPF_REQUIRE(!bad, "mpf_warp_views_blend_next_merge_prev: merge_prev's %s overlaps a buffer this launch reads or writes", outs[k].what);
+    }
+    return 0;
+}
+
+// `next`: the Stage A+C block of the next image as the caller passed it; T, plane_stride and sigma_off are set here
+static int pair_launch_impl(const float *d_rgba, const MpfWarpView *views, const MpfViewSupport *supports, int n_views, const MpfSbfArgs &next, int P,
+                            int S, int H, int W, const MpfMergeArgs *merge_prev, void *stream)
+{
+    MpfMergeArgs mg;
+    memset(&mg, 0, sizeof(mg));
+    if (merge_prev) {
+        mg = *merge_prev;
+        if (const int rc = merge_prev_check(mg, d_rgba, views, n_views, next, P, S, H, W)) return rc;
+    }
+    MPF_REQUIRE(d_rgba && views && next.mpi && next.img && next.params && next.out_rgba, "mpf_warp_views_and_blend_next: null pointer");
+    MPF_REQUIRE(next.out_rgba != d_rgba, "mpf_warp_views_and_blend_next: the stack being rendered and the stack being written must be different buffers");
+    MPF_REQUIRE(n_views >= 1 && n_views <= MPF_MAX_VIEWS, "mpf_warp_views_and_blend_next: n_views must be 1..%d (got %d)", MPF_MAX_VIEWS, n_views);
+    MPF_REQUIRE(S >= 1 && S < 4096 && H >= 1 && W >= 1, "mpf_warp_views_and_blend_next: bad shape S=%d H=%d W=%d", S, H, W);
+    MPF_REQUIRE((int64_t)H * W < ((int64_t)1 << 27), "mpf_warp_views_and_blend_next: H*W too large for 32-bit byte offsets");
+    MPF_REQUIRE((int64_t)S * H * W * 16 < ((int64_t)1 << 32), "mpf_warp_views_and_blend_next: the plane stack must be smaller than 4 GiB (buffer addressing); use the two separate calls");
+    MPF_REQUIRE(mpf_aligned16(d_rgba) && mpf_aligned16(next.out_rgba), "mpf_warp_views_and_blend_next: the stacks must be 16-byte aligned");
+    MPF_REQUIRE(P >= 0 && P <= 2 && (P == 0) == (next.flows == nullptr), "mpf_warp_views_and_blend_next: P must be 0..2, flows output iff P > 0");
+    MPF_REQUIRE((next.quads == nullptr && next.quads_c == nullptr) || next.obj_mask, "mpf_warp_views_and_blend_next: quads need d_obj_mask_next");
+    MPF_REQUIRE(mpf_aligned16(next.quads) && mpf_aligned16(next.quads_c), "mpf_warp_views_and_blend_next: quads must be 16-byte aligned");
+    MPF_REQUIRE((next.sup == nullptr || next.quads) && (next.sup_c == nullptr || next.quads_c), "mpf_warp_views_and_blend_next: a support map needs its quads");
+    for (int v = 0; supports && v < n_views; ++v)          // the two halves of the launch are unordered: a map being written cannot be one being tested
+        MPF_REQUIRE(!supports[v].d_cells || (supports[v].d_cells != next.sup && supports[v].d_cells != next.sup_c),
+                    "mpf_warp_views_and_blend_next: view %d tests a support map this launch writes", v);
+    MpfViewSet vs;
+    bool has_mask;
+    if (const int rc = view_set("mpf_warp_views_and_blend_next", views, n_views, vs, has_mask)) return rc;
+    const int64_t N = (int64_t)H * W;
+    MpfSbfArgs ac = next;
+    ac.T = (N + MPF_OVL_PX - 1) / MPF_OVL_PX;
+    if (!ac.quads && !ac.quads_c) ac.obj_mask = nullptr;   // the mask is read for the quads only
+    ac.plane_stride = 4 * N; ac.sigma_off = 3 * N;         // the [S,4,H,W] stack
+    const MpfSupportSet ss = mpf_support_set(views, supports, n_views, has_mask);
+    hipStream_t st = (hipStream_t)stream;
+#define MPF_OVL(HM, NLv)                                                                                                        \
+    switch (P) {                                                                                                                \
+    case 0: return ac.cum_mask ? launch_overlap<HM, NLv, 0, true>(d_rgba, vs, n_views, ac, S, H, W, st, mg, ss) : launch_overlap<HM, NLv, 0, false>(d_rgba, vs, n_views, ac, S, H, W, st, mg, ss); \
+    case 1: return ac.cum_mask ? launch_overlap<HM, NLv, 1, true>(d_rgba, vs, n_views, ac, S, H, W, st, mg, ss) : launch_overlap<HM, NLv, 1, false>(d_rgba, vs, n_views, ac, S, H, W, st, mg, ss); \
+    default: return ac.cum_mask ? launch_overlap<HM, NLv, 2, true>(d_rgba, vs, n_views, ac, S, H, W, st, mg, ss) : launch_overlap<HM, NLv, 2, false>(d_rgba, vs, n_views, ac, S, H, W, st, mg, ss); \
+    }
+    if (S < 256) { if (has_mask) { MPF_OVL(true, 2) } else { MPF_OVL(false, 2) } }
+    else         { if (has_mask) { MPF_OVL(true, 3) } else { MPF_OVL(false, 3) } }
+#undef MPF_OVL
+}
+
 extern "C" int mpf_warp_views_and_blend_next(const float *d_rgba, const MpfWarpView *views, int n_views,
                                              const float *d_mpi_next, const float *d_img_next, const float *d_params_next, int P,
                                              float flow_clip, float *d_out_rgba_next, float *d_flows_next, uint8_t *d_src_u8_bgr_next,
@@ -2130,21 +2234,15 @@ extern "C" int mpf_warp_views_and_blend_next(const float *d_rgba, const MpfWarpV
                                                 d_src_u8_bgr_next, d_obj_mask_next, d_quads_next, d_quads_complement_next, d_cum_mask_next, S, H, W, nullptr, stream);
 }
 
-static int pair_launch_impl(const float *d_rgba, const MpfWarpView *views, const MpfViewSupport *supports, int n_views,
-                            const float *d_mpi_next, const float *d_img_next, const float *d_params_next, int P,
-                            float flow_clip, float *d_out_rgba_next, float *d_flows_next, uint8_t *d_src_u8_bgr_next,
-                            const float *d_obj_mask_next, float *d_quads_next, float *d_quads_complement_next,
-                            const float *d_cum_mask_next, unsigned *d_support_next, unsigned *d_support_complement_next, unsigned tag_next,
-                            int S, int H, int W, const MpfMergeArgs *merge_prev, void *stream);
-
 extern "C" int mpf_warp_views_blend_next_merge_prev(const float *d_rgba, const MpfWarpView *views, int n_views,
                                                     const float *d_mpi_next, const float *d_img_next, const float *d_params_next, int P,
                                                     float flow_clip, float *d_out_rgba_next, float *d_flows_next, uint8_t *d_src_u8_bgr_next,
                                                     const float *d_obj_mask_next, float *d_quads_next, float *d_quads_complement_next,
                                                     const float *d_cum_mask_next, int S, int H, int W, const MpfMergeArgs *merge_prev, void *stream)
 {
-    return pair_launch_impl(d_rgba, views, nullptr, n_views, d_mpi_next, d_img_next, d_params_next, P, flow_clip, d_out_rgba_next, d_flows_next, d_src_u8_bgr_next,
-                            d_obj_mask_next, d_quads_next, d_quads_complement_next, d_cum_mask_next, nullptr, nullptr, 0, S, H, W, merge_prev, stream);
+    const MpfSbfArgs next = { d_mpi_next, d_img_next, d_params_next, flow_clip, d_out_rgba_next, nullptr, nullptr, d_flows_next, 0, d_src_u8_bgr_next, d_obj_mask_next,
+                              reinterpret_cast<float4 *>(d_quads_next), reinterpret_cast<float4 *>(d_quads_complement_next), d_cum_mask_next, 0, 0, nullptr, nullptr, 0 };
+    return pair_launch_impl(d_rgba, views, nullptr, n_views, next, P, S, H, W, merge_prev, stream);
 }
 
 extern "C" int mpf_warp_views_blend_next_merge_prev_support(const float *d_rgba, const MpfWarpView *views, const MpfViewSupport *supports, int n_views,
@@ -2154,107 +2252,10 @@ extern "C" int mpf_warp_views_blend_next_merge_prev_support(const float *d_rgba,
                                                             const float *d_cum_mask_next, uint32_t *d_support_next, uint32_t *d_support_complement_next,
                                                             uint32_t tag_next, int S, int H, int W, const MpfMergeArgs *merge_prev, void *stream)
 {
-    return pair_launch_impl(d_rgba, views, supports, n_views, d_mpi_next, d_img_next, d_params_next, P, flow_clip, d_out_rgba_next, d_flows_next, d_src_u8_bgr_next,
-                            d_obj_mask_next, d_quads_next, d_quads_complement_next, d_cum_mask_next, d_support_next, d_support_complement_next, tag_next, S, H, W,
-                            merge_prev, stream);
-}
-
-static int pair_launch_impl(const float *d_rgba, const MpfWarpView *views, const MpfViewSupport *supports, int n_views,
-                            const float *d_mpi_next, const float *d_img_next, const float *d_params_next, int P,
-                            float flow_clip, float *d_out_rgba_next, float *d_flows_next, uint8_t *d_src_u8_bgr_next,
-                            const float *d_obj_mask_next, float *d_quads_next, float *d_quads_complement_next,
-                            const float *d_cum_mask_next, unsigned *d_support_next, unsigned *d_support_complement_next, unsigned tag_next,
-                            int S, int H, int W, const MpfMergeArgs *merge_prev, void *stream)
-{
-    MpfMergeArgs mg;
-    memset(&mg, 0, sizeof(mg));
-    if (merge_prev) {
-        mg = *merge_prev;
-        MPF_REQUIRE(mg.d_frame && mg.d_frame_dyn && mg.d_mask && mg.d_mask_dyn && mg.d_flow && mg.d_flow_dyn && mg.d_obj_mask && mg.d_flow_mix && mg.d_frame_mix &&
-                        mg.d_fill_mask, "mpf_warp_views_blend_next_merge_prev: merge_prev has a null pointer");
-        for (int v = 0; v < n_views && views; ++v)
-            MPF_REQUIRE(views[v].d_rgb != mg.d_frame && views[v].d_rgb != mg.d_frame_dyn && views[v].d_objmask != mg.d_mask && views[v].d_objmask != mg.d_mask_dyn,
-                        "mpf_warp_views_blend_next_merge_prev: the merged pair's views must not be the views this launch renders");
-        MPF_REQUIRE(mg.obj_mask_stride >= 0 && mg.obj_mask_stride <= 4, "mpf_warp_views_blend_next_merge_prev: obj_mask_stride must be 0..4");
-        // The folded merge is race-free only if (1) the thread that merges pixel n is the ONLY one that writes anything the merge of pixel n reads:
-        // the merged pair's flows are either disjoint from the flows this launch writes or exactly those planes (d_flows_next + {0, 2N}: same pixel,
-        // same thread, read before written), its object mask is disjoint from the launch's outputs or exactly the .x of d_quads_next (same argument),
-        // and (2) what the merge writes overlaps nothing this launch reads or writes.
-        const size_t Nn = (size_t)H * W;
-        auto overlaps = [](const void *a, size_t an, const void *b, size_t bn) {
-            return a && b && (const char *)a < (const char *)b + bn && (const char *)b < (const char *)a + an;
-        };
-        const size_t flows_next_bytes = (size_t)P * 2 * Nn * sizeof(float);
-        const float *fl[2] = { mg.d_flow, mg.d_flow_dyn };
-        for (int k = 0; k < 2; ++k) {
-            const bool aligned = d_flows_next && P == 2 && (fl[k] == d_flows_next || fl[k] == d_flows_next + 2 * Nn);
-            MPF_REQUIRE(aligned || !overlaps(fl[k], 2 * Nn * sizeof(float), d_flows_next, flows_next_bytes),
-                        "mpf_warp_views_blend_next_merge_prev: merge_prev's flows must be disjoint from d_flows_next or exactly its two pose planes");
-        }
-        const size_t om_bytes = Nn * sizeof(float) * (size_t)(mg.obj_mask_stride > 1 ? mg.obj_mask_stride : 1);
-        const bool om_is_quads = mg.obj_mask_stride == 4 && (const void *)mg.d_obj_mask == (const void *)d_quads_next;
-        MPF_REQUIRE(om_is_quads || (!overlaps(mg.d_obj_mask, om_bytes, d_quads_next, Nn * 16) && !overlaps(mg.d_obj_mask, om_bytes, d_quads_complement_next, Nn * 16) &&
-                                    !overlaps(mg.d_obj_mask, om_bytes, d_out_rgba_next, (size_t)S * Nn * 16) && !overlaps(mg.d_obj_mask, om_bytes, d_flows_next, flows_next_bytes)),
-                    "mpf_warp_views_blend_next_merge_prev: merge_prev's object mask must not be a buffer this launch writes (other than the .x of d_quads_next, stride 4)");
-        const struct { const void *p; size_t n; const char *what; } outs[3] = { { mg.d_flow_mix, 2 * Nn * sizeof(float), "flow_mix" }, { mg.d_frame_mix, 3 * Nn, "frame_mix" },
-                                                                                  { mg.d_fill_mask, Nn, "fill_mask" } };
-        for (int k = 0; k < 3; ++k) {
-            bool bad = overlaps(outs[k].p, outs[k].n, d_out_rgba_next, (size_t)S * Nn * 16) || overlaps(outs[k].p, outs[k].n, d_rgba, (size_t)S * Nn * 16) ||
-                       overlaps(outs[k].p, outs[k].n, d_flows_next, flows_next_bytes) || overlaps(outs[k].p, outs[k].n, d_quads_next, Nn * 16) ||
-                       overlaps(outs[k].p, outs[k].n, d_quads_complement_next, Nn * 16) || overlaps(outs[k].p, outs[k].n, d_src_u8_bgr_next, 3 * Nn) ||
-                       overlaps(outs[k].p, outs[k].n, d_obj_mask_next, Nn * 4) || overlaps(outs[k].p, outs[k].n, mg.d_obj_mask, om_bytes) ||
-                       overlaps(outs[k].p, outs[k].n, mg.d_flow, 2 * Nn * 4) || overlaps(outs[k].p, outs[k].n, mg.d_flow_dyn, 2 * Nn * 4) ||
-                       overlaps(outs[k].p, outs[k].n, mg.d_frame, 3 * Nn * 4) || overlaps(outs[k].p, outs[k].n, mg.d_frame_dyn, 3 * Nn * 4) ||
-                       overlaps(outs[k].p, outs[k].n, mg.d_mask, Nn * 4) || overlaps(outs[k].p, outs[k].n, mg.d_mask_dyn, Nn * 4);
-            for (int j = k + 1; j < 3; ++j) bad = bad || overlaps(outs[k].p, outs[k].n, outs[j].p, outs[j].n);
-            for (int v = 0; v < n_views && views; ++v)
-                bad = bad || overlaps(outs[k].p, outs[k].n, views[v].d_rgb, 3 * Nn * 4) || overlaps(outs[k].p, outs[k].n, views[v].d_objmask, Nn * 4) ||
-                      overlaps(outs[k].p, outs[k].n, views[v].d_depth, Nn * 4) || overlaps(outs[k].p, outs[k].n, views[v].d_tgt_mask, Nn * 4) ||
-                      overlaps(outs[k].p, outs[k].n, views[v].d_rgb_u8_bgr, 3 * Nn) || overlaps(outs[k].p, outs[k].n, views[v].d_mask_quads, Nn * 16);
-            MPF_REQUIRE(!bad, "mpf_warp_views_blend_next_merge_prev: merge_prev's %s overlaps a buffer this launch reads or writes", outs[k].what);
-        }
-    }
-    MPF_REQUIRE(d_rgba && views && d_mpi_next && d_img_next && d_params_next && d_out_rgba_next, "mpf_warp_views_and_blend_next: null pointer");
-    MPF_REQUIRE(d_out_rgba_next != d_rgba, "mpf_warp_views_and_blend_next: the stack being rendered and the stack being written must be different buffers");
-    MPF_REQUIRE(n_views >= 1 && n_views <= MPF_MAX_VIEWS, "mpf_warp_views_and_blend_next: n_views must be 1..%d (got %d)", MPF_MAX_VIEWS, n_views);
-    MPF_REQUIRE(S >= 1 && S < 4096 && H >= 1 && W >= 1, "mpf_warp_views_and_blend_next: bad shape S=%d H=%d W=%d", S, H, W);
-    MPF_REQUIRE((int64_t)H * W < ((int64_t)1 << 27), "mpf_warp_views_and_blend_next: H*W too large for 32-bit byte offsets");
-    MPF_REQUIRE((int64_t)S * H * W * 16 < ((int64_t)1 << 32), "mpf_warp_views_and_blend_next: the plane stack must be smaller than 4 GiB (buffer addressing); use the two separate calls");
-    MPF_REQUIRE(mpf_aligned16(d_rgba) && mpf_aligned16(d_out_rgba_next), "mpf_warp_views_and_blend_next: the stacks must be 16-byte aligned");
-    MPF_REQUIRE(P >= 0 && P <= 2 && (P == 0) == (d_flows_next == nullptr), "mpf_warp_views_and_blend_next: P must be 0..2, flows output iff P > 0");
-    MPF_REQUIRE((d_quads_next == nullptr && d_quads_complement_next == nullptr) || d_obj_mask_next, "mpf_warp_views_and_blend_next: quads need d_obj_mask_next");
-    MPF_REQUIRE(mpf_aligned16(d_quads_next) && mpf_aligned16(d_quads_complement_next), "mpf_warp_views_and_blend_next: quads must be 16-byte aligned");
-    MPF_REQUIRE((d_support_next == nullptr || d_quads_next) && (d_support_complement_next == nullptr || d_quads_complement_next),
-                "mpf_warp_views_and_blend_next: a support map needs its quads");
-    for (int v = 0; supports && v < n_views; ++v)          // the two halves of the launch are unordered: a map being written cannot be one being tested
-        MPF_REQUIRE(!supports[v].d_cells || (supports[v].d_cells != d_support_next && supports[v].d_cells != d_support_complement_next),
-                    "mpf_warp_views_and_blend_next: view %d tests a support map this launch writes", v);
-    MpfViewSet vs;
-    memset(&vs, 0, sizeof(vs));
-    const bool has_mask = views[0].d_mask_quads != nullptr;
-    for (int v = 0; v < n_views; ++v) {
-        const MpfWarpView &w = views[v];
-        MPF_REQUIRE(w.d_params && w.d_rgb, "mpf_warp_views_and_blend_next: view %d: null params / rgb", v);
-        MPF_REQUIRE((w.d_mask_quads != nullptr) == has_mask, "mpf_warp_views_and_blend_next: all views of a call take a mask, or none does");
-        MPF_REQUIRE((w.d_mask_quads == nullptr) == (w.d_objmask == nullptr), "mpf_warp_views_and_blend_next: view %d: mask quads and objmask output go together", v);
-        MPF_REQUIRE(mpf_aligned16(w.d_mask_quads), "mpf_warp_views_and_blend_next: view %d: mask quads must be 16-byte aligned", v);
-        vs.v[v] = w;
-    }
-    const int64_t N = (int64_t)H * W;
-    const MpfSbfArgs ac = { d_mpi_next, d_img_next, d_params_next, flow_clip, d_out_rgba_next, nullptr, nullptr, d_flows_next, (N + MPF_OVL_PX - 1) / MPF_OVL_PX, d_src_u8_bgr_next,
-                            (d_quads_next || d_quads_complement_next) ? d_obj_mask_next : nullptr, reinterpret_cast<float4 *>(d_quads_next),
-                            reinterpret_cast<float4 *>(d_quads_complement_next), d_cum_mask_next, 4 * N, 3 * N, d_support_next, d_support_complement_next, tag_next };
-    const MpfSupportSet ss = mpf_support_set(views, supports, n_views, has_mask);
-    hipStream_t st = (hipStream_t)stream;
-#define MPF_OVL(HM, NLv)                                                                                                        \
-    switch (P) {                                                                                                                \
-    case 0: return d_cum_mask_next ? launch_overlap<HM, NLv, 0, true>(d_rgba, vs, n_views, ac, S, H, W, st, mg, ss) : launch_overlap<HM, NLv, 0, false>(d_rgba, vs, n_views, ac, S, H, W, st, mg, ss); \
-    case 1: return d_cum_mask_next ? launch_overlap<HM, NLv, 1, true>(d_rgba, vs, n_views, ac, S, H, W, st, mg, ss) : launch_overlap<HM, NLv, 1, false>(d_rgba, vs, n_views, ac, S, H, W, st, mg, ss); \
-    default: return d_cum_mask_next ? launch_overlap<HM, NLv, 2, true>(d_rgba, vs, n_views, ac, S, H, W, st, mg, ss) : launch_overlap<HM, NLv, 2, false>(d_rgba, vs, n_views, ac, S, H, W, st, mg, ss); \
-    }
-    if (S < 256) { if (has_mask) { MPF_OVL(true, 2) } else { MPF_OVL(false, 2) } }
-    else         { if (has_mask) { MPF_OVL(true, 3) } else { MPF_OVL(false, 3) } }
-#undef MPF_OVL
+    const MpfSbfArgs next = { d_mpi_next, d_img_next, d_params_next, flow_clip, d_out_rgba_next, nullptr, nullptr, d_flows_next, 0, d_src_u8_bgr_next, d_obj_mask_next,
+                              reinterpret_cast<float4 *>(d_quads_next), reinterpret_cast<float4 *>(d_quads_complement_next), d_cum_mask_next, 0, 0, d_support_next,
+                              d_support_complement_next, tag_next };
+    return pair_launch_impl(d_rgba, views, supports, n_views, next, P, S, H, W, merge_prev, stream);
 }
 
 // hard_flow = True (utils/mpi/mpi_rendering.py:126-130): the flow of the arg-max-weight plane instead of the weighted sum.  One pass over the
@@ -2350,8 +2351,11 @@ extern "C" int mpf_src_flow(const float *d_sigma_SHW, const float *d_params, int
     const int64_t N = (int64_t)H * W;
     hipStream_t st = (hipStream_t)stream;
     // flow-only body (BLEND = false): reads nothing but the sigma planes; no image, no by-products
-    if (P == 1) return launch_sbf<1, 1>(d_sigma_SHW, nullptr, d_params, S, H, W, flow_clip, nullptr, nullptr, nullptr, d_flows, nullptr, nullptr, nullptr, nullptr, nullptr, st, N, 0);
-    return launch_sbf<1, 2>(d_sigma_SHW, nullptr, d_params, S, H, W, flow_clip, nullptr, nullptr, nullptr, d_flows, nullptr, nullptr, nullptr, nullptr, nullptr, st, N, 0);
+    MpfSbfArgs a = {};
+    a.mpi = d_sigma_SHW; a.params = d_params; a.flow_clip = flow_clip; a.flows = d_flows;
+    a.plane_stride = N; a.sigma_off = 0;                   // the bare sigma tensor [S,H,W]
+    if (P == 1) return launch_sbf<1, 1>(a, S, H, W, st);
+    return launch_sbf<1, 2>(a, S, H, W, st);
 }
 
 #ifdef MPF_WITNESS

@@ -107,12 +107,9 @@ def src_blend_flow(mpi_S4HW, img_3HW, K_inv=None, depth_S=None, homs_tgt_src=Non
     args = [_ptr(mpi), _ptr(img), _ptr(dparams), P, S, H, W, float(flow_clip), _ptr(rgba), _ptr(planar), _ptr(tacc), _ptr(flows), _ptr(src_u8),
             _ptr(_dev(obj_mask, "obj_mask").reshape(H, W)) if obj_mask is not None else None, _ptr(quads), _ptr(quads_complement),
             _ptr(_dev(cum_mask, "cum_mask")) if cum_mask is not None else None]
-    if support is not None or support_complement is not None:
-        _check_support_map(support, H, W, mpi.device)
-        _check_support_map(support_complement, H, W, mpi.device)
-        _lib.check(lib.mpf_src_blend_flow_support(*args, _ptr(support), _ptr(support_complement), int(tag), _stream()), "mpf_src_blend_flow_support")
-    else:
-        _lib.check(lib.mpf_src_blend_flow(*args, _stream()), "mpf_src_blend_flow")
+    _check_support_map(support, H, W, mpi.device)
+    _check_support_map(support_complement, H, W, mpi.device)
+    _lib.check(lib.mpf_src_blend_flow_support(*args, _ptr(support), _ptr(support_complement), int(tag), _stream()), "mpf_src_blend_flow_support")
     return dict(rgba=rgba, rgb_planar=planar, tacc=tacc, flows=flows)
 
 
@@ -280,19 +277,8 @@ def warp_composite_views(rgba, views, interleaved=2):
     assert C == 4 and interleaved in (1, 2) and 1 <= len(views) <= _lib.MAX_VIEWS
     if interleaved == 2:
         assert a.untyped_storage().nbytes() - a.storage_offset() * 4 >= a.numel() * 4 + (W + 1) * 16
-    arr = (_lib.MpfWarpView * len(views))()
-    for i, v in enumerate(views):
-        o = v["out"]
-        q = v.get("quads")
-        for t in [v["dparams"], q] + [o.get(k) for k in ("rgb", "depth", "objmask", "tgt_mask", "rgb_u8")]:
-            assert t is None or (t.is_cuda and t.is_contiguous() and t.device == a.device)
-        arr[i] = _lib.MpfWarpView(v["dparams"].data_ptr(), q.data_ptr() if q is not None else None, o["rgb"].data_ptr(),
-                                  *[(o[k].data_ptr() if o.get(k) is not None else None) for k in ("depth", "objmask", "tgt_mask", "rgb_u8")])
-    sup = _support_array(views, H, W, a.device)
-    if sup is not None:
-        _lib.check(lib.mpf_warp_composite_views_support(_ptr(a), int(interleaved), arr, sup, len(views), S, H, W, _stream()), "mpf_warp_composite_views_support")
-    else:
-        _lib.check(lib.mpf_warp_composite_views(_ptr(a), int(interleaved), arr, len(views), S, H, W, _stream()), "mpf_warp_composite_views")
+    _lib.check(lib.mpf_warp_composite_views_support(_ptr(a), int(interleaved), _view_array(views, a.device), _support_array(views, H, W, a.device), len(views),
+                                                    S, H, W, _stream()), "mpf_warp_composite_views_support")
     return [v["out"] for v in views]
 
 
@@ -332,18 +318,12 @@ def warp_views_and_blend_next(rgba, views, mpi_next, img_next, dparams_next, P, 
     cm = _dev(cum_mask_next, "cum_mask_next") if cum_mask_next is not None else None
     sup = _support_array(views, H, W, a.device)
     mp = ctypes.byref(merge_prev) if merge_prev is not None else None
-    if sup is not None or support_next is not None or support_complement_next is not None:
-        _check_support_map(support_next, H, W, a.device)
-        _check_support_map(support_complement_next, H, W, a.device)
-        _lib.check(lib.mpf_warp_views_blend_next_merge_prev_support(
-            _ptr(a), arr, sup, len(views), _ptr(mpi), _ptr(img), _ptr(dparams_next), int(P), float(flow_clip), _ptr(out_rgba_next), _ptr(out_flows_next),
-            _ptr(src_u8_next), _ptr(om), _ptr(quads_next), _ptr(quads_complement_next), _ptr(cm), _ptr(support_next), _ptr(support_complement_next),
-            int(tag_next), S, H, W, mp, _stream()), "mpf_warp_views_blend_next_merge_prev_support")
-    else:
-        _lib.check(lib.mpf_warp_views_blend_next_merge_prev(_ptr(a), arr, len(views), _ptr(mpi), _ptr(img), _ptr(dparams_next), int(P), float(flow_clip),
-                                                            _ptr(out_rgba_next), _ptr(out_flows_next), _ptr(src_u8_next), _ptr(om), _ptr(quads_next),
-                                                            _ptr(quads_complement_next), _ptr(cm), S, H, W, mp, _stream()),
-                   "mpf_warp_views_blend_next_merge_prev")
+    _check_support_map(support_next, H, W, a.device)
+    _check_support_map(support_complement_next, H, W, a.device)
+    _lib.check(lib.mpf_warp_views_blend_next_merge_prev_support(
+        _ptr(a), arr, sup, len(views), _ptr(mpi), _ptr(img), _ptr(dparams_next), int(P), float(flow_clip), _ptr(out_rgba_next), _ptr(out_flows_next),
+        _ptr(src_u8_next), _ptr(om), _ptr(quads_next), _ptr(quads_complement_next), _ptr(cm), _ptr(support_next), _ptr(support_complement_next),
+        int(tag_next), S, H, W, mp, _stream()), "mpf_warp_views_blend_next_merge_prev_support")
     return [v["out"] for v in views]
 
 
