@@ -40,7 +40,8 @@ extern "C" {
                              round 6 (601): + loader 6 (MPF_CONV_LD_NEAREST_PHASE), mpf_tune("fwarp_gate"), mpf_forward_warp_workspace + 256 bytes;
                              the RAFT entry points added since (mpf_corr_*, mpf_upsample_*, mpf_flow_loss_term*, and now mpf_gru_reset, mpf_gru_update and
                              their _backward calls with MpfGruTerm / MpfGruArgs, and now mpf_norm_stats, mpf_norm_act, mpf_norm_act_backward_reduce and
-                             mpf_norm_act_backward with MpfNormTerm / MpfNormArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
+                             mpf_norm_act_backward with MpfNormTerm / MpfNormArgs, and now mpf_raft_images, mpf_context_split, mpf_upflow8 and
+                             their _backward calls with MpfRaftGlueArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
 
 /* d_params layout (floats):
  *   [0..8]   K_src^-1 (3x3 row-major)            [9..20]  G_tgt_src rows 0..2 (3x4 row-major: R | t)
@@ -623,6 +624,38 @@ int mpf_norm_stats(const MpfNormArgs *a, void *stream);
 int mpf_norm_act(const MpfNormArgs *a, void *stream);
 int mpf_norm_act_backward_reduce(const MpfNormArgs *a, void *stream);
 int mpf_norm_act_backward(const MpfNormArgs *a, void *stream);
+
+/* What RAFT.forward (RAFT/core/raft.py:86-144) does between its modules.  All tensors f32, NCHW, contiguous; every tensor below 2^31 elements.
+ *   mpf_raft_images             pair[2N,3,H,W] <- 2 * (x / 255) - 1 of image1 [N,3,H,W] (first N) and image2 (last N), one launch: the feature
+ *                               network's batch, whose first half is the context network's input.  A true, correctly rounded fp32 division.
+ *   mpf_context_split           cnet [N,hdim+cdim,H,W]: net [N,hdim,H,W] <- tanh(cnet[:, :hdim]), inp [N,cdim,H,W] <- relu(cnet[:, hdim:]), one launch
+ *   mpf_context_split_backward  grad_cnet [N,hdim+cdim,H,W] <- (g_net * (1 - net^2) | g_inp where !(inp <= 0), else 0) from the saved outputs
+ *   mpf_upflow8                 flow [N,2,H,W]: flow_up [N,2,8H,8W] <- 8 * bilinear(flow), align_corners = true (utils/utils.py:80-82): the source
+ *                               coordinate is dst * (H-1)/(8H-1), scale 0 for a size of 1; ATen's upsample_bilinear2d operation for operation
+ *   mpf_upflow8_backward        g_up [N,2,8H,8W]: grad_flow [N,2,H,W] <- per coarse element the weighted sum (fp64, fixed order) over the fine
+ *                               pixels whose footprint touches it
+ * relu(v) = v < 0 ? 0 : v.  16-byte accesses where the sizes and pointers allow, 4-byte ones otherwise: any N, H, W >= 1.  No atomics:
+ * bit-identical from run to run.  Outputs must not overlap inputs.  Validated before anything is launched (MPF_ERR_BAD_ARGUMENT): NULL
+ * pointers the call uses, non-positive sizes, a tensor of 2^31 elements or more. */
+typedef struct MpfRaftGlueArgs {
+    const float *image1, *image2;    /* mpf_raft_images: [N,3,H,W] each */
+    float *pair;                     /* mpf_raft_images: [2N,3,H,W], written */
+    const float *cnet;               /* mpf_context_split: [N,hdim+cdim,H,W] */
+    float *net, *inp;                /* mpf_context_split: written; _backward: read */
+    const float *g_net, *g_inp;      /* mpf_context_split_backward: the cotangents of net and inp */
+    float *grad_cnet;                /* mpf_context_split_backward: [N,hdim+cdim,H,W], written */
+    const float *flow;               /* mpf_upflow8: [N,2,H,W] */
+    float *flow_up;                  /* mpf_upflow8: [N,2,8H,8W], written */
+    const float *g_up;               /* mpf_upflow8_backward: the cotangent [N,2,8H,8W] */
+    float *grad_flow;                /* mpf_upflow8_backward: [N,2,H,W], written */
+    int N, H, W;                     /* mpf_raft_images: the frame; the other calls: the coarse (1/8) map */
+    int hdim, cdim;                  /* the context split */
+} MpfRaftGlueArgs;
+int mpf_raft_images(const MpfRaftGlueArgs *a, void *stream);
+int mpf_context_split(const MpfRaftGlueArgs *a, void *stream);
+int mpf_context_split_backward(const MpfRaftGlueArgs *a, void *stream);
+int mpf_upflow8(const MpfRaftGlueArgs *a, void *stream);
+int mpf_upflow8_backward(const MpfRaftGlueArgs *a, void *stream);
 
 /* [3,H,W] float RGB -> [H,W,3] u8 BGR, clip(rint(x*255))  (utils/utils.py:174-177) */
 int mpf_to_u8_bgr(const float *d_img, int H, int W, uint8_t *d_out, void *stream);

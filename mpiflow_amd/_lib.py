@@ -157,6 +157,13 @@ class MpfNormArgs(ctypes.Structure):
                 ("chunks", c_i), ("N", c_i), ("C", c_i), ("H", c_i), ("W", c_i)]
 
 
+class MpfRaftGlueArgs(ctypes.Structure):
+    """struct MpfRaftGlueArgs of include/mpiflow_hip.h: the glue of RAFT.forward: image scaling, context split, 8x bilinear upsampling."""
+    _fields_ = [("image1", c_p), ("image2", c_p), ("pair", c_p), ("cnet", c_p), ("net", c_p), ("inp", c_p), ("g_net", c_p), ("g_inp", c_p),
+                ("grad_cnet", c_p), ("flow", c_p), ("flow_up", c_p), ("g_up", c_p), ("grad_flow", c_p),
+                ("N", c_i), ("H", c_i), ("W", c_i), ("hdim", c_i), ("cdim", c_i)]
+
+
 MAX_VIEWS = 16          # MPF_MAX_VIEWS
 SUPPORT_CELL_W, SUPPORT_CELL_H = 32, 8      # MPF_SUPPORT_CELL_W / _H
 
@@ -218,6 +225,11 @@ SIGNATURES = {
     "mpf_norm_act": (c_i, [ctypes.POINTER(MpfNormArgs), c_p]),
     "mpf_norm_act_backward_reduce": (c_i, [ctypes.POINTER(MpfNormArgs), c_p]),
     "mpf_norm_act_backward": (c_i, [ctypes.POINTER(MpfNormArgs), c_p]),
+    "mpf_raft_images": (c_i, [ctypes.POINTER(MpfRaftGlueArgs), c_p]),
+    "mpf_context_split": (c_i, [ctypes.POINTER(MpfRaftGlueArgs), c_p]),
+    "mpf_context_split_backward": (c_i, [ctypes.POINTER(MpfRaftGlueArgs), c_p]),
+    "mpf_upflow8": (c_i, [ctypes.POINTER(MpfRaftGlueArgs), c_p]),
+    "mpf_upflow8_backward": (c_i, [ctypes.POINTER(MpfRaftGlueArgs), c_p]),
     "mpf_src_xyz": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
     "mpf_transform_xyz": (c_i, [c_p, c_p, c_i, c_i64, c_p, c_p]),
     "mpf_homography_sample": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),

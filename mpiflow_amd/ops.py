@@ -1207,6 +1207,97 @@ def _norm_act_backward(device, grad_out, term, residual, chunks, dres, param_gra
 
 
 @_on_device
+def raft_images(image1, image2):
+    """mpf_raft_images: 2 * (x / 255) - 1 of both [N,3,H,W] image batches in one launch -> the [2N,3,H,W] batch RAFT's feature network takes
+    (image1 first); its first N samples are what the context network takes.  A true fp32 division.  float32, contiguous, on the GPU, or
+    MpiFlowHipError.  Asynchronous on the current stream."""
+    who = "raft_images"
+    im1 = check_tensor(image1, "image1", who, (None, 3, None, None))
+    im2 = check_tensor(image2, "image2", who, tuple(im1.shape))
+    check_devices(who, dict(image1=im1, image2=im2))
+    N, _, H, W = im1.shape
+    pair = torch.empty((2 * N, 3, H, W), dtype=_f32, device=im1.device)
+    a = _lib.MpfRaftGlueArgs()
+    a.image1, a.image2, a.pair, a.N, a.H, a.W = im1.data_ptr(), im2.data_ptr(), pair.data_ptr(), N, H, W
+    _lib.check(_lib.load().mpf_raft_images(ctypes.byref(a), _stream()), "mpf_raft_images")
+    return pair
+
+
+def _split_args(net, inp, who):
+    """MpfRaftGlueArgs with net [N,hdim,H,W] and inp [N,cdim,H,W]"""
+    net = check_tensor(net, "net", who, 4, "[N,hdim,H,W]")
+    N, hdim, H, W = net.shape
+    inp = check_tensor(inp, "inp", who, (N, None, H, W))
+    a = _lib.MpfRaftGlueArgs()
+    a.net, a.inp, a.N, a.H, a.W, a.hdim, a.cdim = net.data_ptr(), inp.data_ptr(), N, H, W, hdim, inp.shape[1]
+    return a
+
+
+@_on_device
+def context_split(cnet, hdim):
+    """mpf_context_split: cnet [N,hdim+cdim,H,W] -> (tanh(cnet[:, :hdim]), relu(cnet[:, hdim:])), both contiguous, one launch."""
+    who = "context_split"
+    cnet = check_tensor(cnet, "cnet", who, 4, "[N,hdim+cdim,H,W]")
+    N, C, H, W = cnet.shape
+    if not 1 <= int(hdim) < C:
+        raise _lib.MpiFlowHipError("%s: hdim must be 1..%d, fewer than cnet's channels (got %s for shape %s)" % (who, C - 1, hdim, tuple(cnet.shape)))
+    check_devices(who, dict(cnet=cnet))
+    net = torch.empty((N, int(hdim), H, W), dtype=_f32, device=cnet.device)
+    inp = torch.empty((N, C - int(hdim), H, W), dtype=_f32, device=cnet.device)
+    a = _split_args(net, inp, who)
+    a.cnet = cnet.data_ptr()
+    _lib.check(_lib.load().mpf_context_split(ctypes.byref(a), _stream()), "mpf_context_split")
+    return net, inp
+
+
+@_on_device
+def context_split_backward(net, inp, g_net, g_inp):
+    """mpf_context_split_backward: the cotangents of context_split's outputs -> grad_cnet [N,hdim+cdim,H,W], recomputed from the outputs
+    themselves (1 - net^2; inp > 0) and written as one tensor."""
+    who = "context_split_backward"
+    a = _split_args(net, inp, who)
+    g_net = check_tensor(g_net, "g_net", who, tuple(net.shape))
+    g_inp = check_tensor(g_inp, "g_inp", who, tuple(inp.shape))
+    check_devices(who, dict(net=net, inp=inp, g_net=g_net, g_inp=g_inp))
+    grad = torch.empty((a.N, a.hdim + a.cdim, a.H, a.W), dtype=_f32, device=net.device)
+    a.g_net, a.g_inp, a.grad_cnet = g_net.data_ptr(), g_inp.data_ptr(), grad.data_ptr()
+    _lib.check(_lib.load().mpf_context_split_backward(ctypes.byref(a), _stream()), "mpf_context_split_backward")
+    return grad
+
+
+@_on_device
+def upflow8(flow):
+    """mpf_upflow8: RAFT's upflow8 (the small model's upsampling): flow [N,2,H,W] -> 8 * F.interpolate(flow, (8H, 8W), mode='bilinear',
+    align_corners=True).  float32, contiguous, on the GPU, or MpiFlowHipError.  Asynchronous on the current stream."""
+    who = "upflow8"
+    flow = check_tensor(flow, "flow", who, (None, 2, None, None))
+    check_devices(who, dict(flow=flow))
+    N, _, H, W = flow.shape
+    out = torch.empty((N, 2, 8 * H, 8 * W), dtype=_f32, device=flow.device)
+    a = _lib.MpfRaftGlueArgs()
+    a.flow, a.flow_up, a.N, a.H, a.W = flow.data_ptr(), out.data_ptr(), N, H, W
+    _lib.check(_lib.load().mpf_upflow8(ctypes.byref(a), _stream()), "mpf_upflow8")
+    return out
+
+
+@_on_device
+def upflow8_backward(grad_out):
+    """mpf_upflow8_backward: the cotangent grad_out [N,2,8H,8W] of upflow8 -> grad_flow [N,2,H,W]; a gather, no atomics: bit-identical from
+    run to run."""
+    who = "upflow8_backward"
+    g = check_tensor(grad_out, "grad_out", who, (None, 2, None, None))
+    N, _, H8, W8 = g.shape
+    if H8 % 8 or W8 % 8:
+        raise _lib.MpiFlowHipError("%s: grad_out must be [N,2,8H,8W] (got shape %s)" % (who, tuple(g.shape)))
+    check_devices(who, dict(grad_out=g))
+    grad = torch.empty((N, 2, H8 // 8, W8 // 8), dtype=_f32, device=g.device)
+    a = _lib.MpfRaftGlueArgs()
+    a.g_up, a.grad_flow, a.N, a.H, a.W = g.data_ptr(), grad.data_ptr(), N, H8 // 8, W8 // 8
+    _lib.check(_lib.load().mpf_upflow8_backward(ctypes.byref(a), _stream()), "mpf_upflow8_backward")
+    return grad
+
+
+@_on_device
 def to_u8_bgr(img_3HW):
     lib = _lib.load()
     img = _dev(img_3HW, "img")

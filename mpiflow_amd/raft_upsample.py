@@ -12,6 +12,7 @@ Two ways in:
 (a) replaces the softmax / unfold / product / sum / permute chain, and the [N,2,9,8,8,H,W] product it keeps for backward, by one kernel each
 way.  (b) goes further: a prediction is blended in registers, compared with the ground truth and summed, and never exists in memory; the
 backward pass recomputes it.  Each prediction is ONE autograd node that saves only its inputs, so backward frees iteration by iteration.
+`upflow8` is the small model's upsampling (no mask: 8 x bilinear, align_corners=True), one kernel each way.
 
 What differs from upstream: `sequence_loss` takes (flows, masks) instead of the upsampled predictions; its sums are folded in fp64 in a fixed
 order (upstream: torch's fp32 mean), so results are bit-identical from run to run; the four metrics cost one device-to-host copy of five
@@ -55,6 +56,23 @@ class _LossTerm(torch.autograd.Function):
         flow, mask, flow_gt, valid = ctx.saved_tensors
         gf, gm = ops.flow_loss_term_backward(flow, mask, flow_gt, valid, g.contiguous(), ctx.max_flow)
         return gf, gm, None, None, None, None
+
+
+class _Upflow8(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flow):
+        return ops.upflow8(flow)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return ops.upflow8_backward(grad_out.contiguous())
+
+
+def upflow8(flow):
+    """RAFT/core/utils/utils.py's upflow8, what the small model upsamples with: flow [N,2,H,W] -> 8 * F.interpolate(flow, (8H, 8W),
+    mode='bilinear', align_corners=True), differentiable.  One kernel each way (mpf_upflow8, mpf_upflow8_backward: a gather, no atomics).
+    float32, contiguous, on the GPU."""
+    return _Upflow8.apply(flow)
 
 
 def upsample_flow(flow, mask):
