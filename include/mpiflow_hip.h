@@ -41,7 +41,8 @@ extern "C" {
                              the RAFT entry points added since (mpf_corr_*, mpf_upsample_*, mpf_flow_loss_term*, and now mpf_gru_reset, mpf_gru_update and
                              their _backward calls with MpfGruTerm / MpfGruArgs, and now mpf_norm_stats, mpf_norm_act, mpf_norm_act_backward_reduce and
                              mpf_norm_act_backward with MpfNormTerm / MpfNormArgs, and now mpf_raft_images, mpf_context_split, mpf_upflow8 and
-                             their _backward calls with MpfRaftGlueArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
+                             their _backward calls with MpfRaftGlueArgs, and now mpf_upflow8_loss_term, its _backward call and
+                             mpf_upflow8_loss_workspace with MpfUpsampleArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
 
 /* d_params layout (floats):
  *   [0..8]   K_src^-1 (3x3 row-major)            [9..20]  G_tgt_src rows 0..2 (3x4 row-major: R | t)
@@ -522,6 +523,22 @@ int mpf_upsample_flow(const MpfUpsampleArgs *a, void *stream);
 int mpf_upsample_flow_backward(const MpfUpsampleArgs *a, void *stream);
 int mpf_flow_loss_term(const MpfUpsampleArgs *a, void *stream);
 int mpf_flow_loss_term_backward(const MpfUpsampleArgs *a, void *stream);
+
+/* The same loss term for the small model, which has no mask: its prediction is upflow8(flow) = 8 * bilinear(flow), align_corners = true (mpf_upflow8
+ * below, whose coordinate arithmetic these calls share operation for operation: the scale (H-1)/(8H-1) rounded once in fp32, 0 for H == 1).
+ * They take the same MpfUpsampleArgs; mask, out and grad_mask are ignored.
+ * mpf_upflow8_loss_term           flow [N,2,H,W], flow_gt [N,2,8H,8W], valid [N,8H,8W], max_flow; the prediction is formed in registers and never
+ *                                 stored.  v, S, term[0] = S / (N*2*8H*8W) and, with metrics != NULL, the five f64 accumulators: as mpf_flow_loss_term.
+ * mpf_upflow8_loss_term_backward  g: ONE f32 on the device.  WRITES grad_flow [N,2,H,W] for the cotangent g / (N*2*8H*8W) * v * sign(pred - flow_gt),
+ *                                 sign(0) = 0 and a NaN difference gives 0.  The prediction is recomputed; nothing of full-resolution size is written.
+ *                                 A gather per coarse pixel over the fine pixels that read it, summed in fp64 in a fixed order.
+ * workspace: mpf_upflow8_loss_workspace(N, H, W, backward) bytes, 8-byte aligned (backward = 0: per-block partials; backward = 1: 0, the gather needs
+ * none and the field is ignored).  No atomics: every output is bit-identical from run to run.
+ * Any N, H, W >= 1 with N*2*8H*8W < 2^31; flow_gt and valid 16-byte aligned.  Tensor VALUES are unrestricted: NaN and inf propagate as they do in
+ * torch and no value changes an address.  Validated before anything is launched (MPF_ERR_BAD_ARGUMENT). */
+size_t mpf_upflow8_loss_workspace(int N, int H, int W, int backward);   /* 0 for a shape the calls refuse; 0 for backward */
+int mpf_upflow8_loss_term(const MpfUpsampleArgs *a, void *stream);
+int mpf_upflow8_loss_term_backward(const MpfUpsampleArgs *a, void *stream);
 
 /* The pointwise work of RAFT's convolutional GRU (ConvGRU / SepConvGRU, RAFT/core/update.py:16-60) between its gate convolutions, fused.
  * All tensors f32, NCHW, contiguous.  A pre-activation is the sum of up to MPF_GRU_MAX_TERMS terms; a term is the channel slice

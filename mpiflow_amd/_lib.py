@@ -217,6 +217,9 @@ SIGNATURES = {
     "mpf_upsample_flow_backward": (c_i, [ctypes.POINTER(MpfUpsampleArgs), c_p]),
     "mpf_flow_loss_term": (c_i, [ctypes.POINTER(MpfUpsampleArgs), c_p]),
     "mpf_flow_loss_term_backward": (c_i, [ctypes.POINTER(MpfUpsampleArgs), c_p]),
+    "mpf_upflow8_loss_workspace": (c_sz, [c_i, c_i, c_i, c_i]),
+    "mpf_upflow8_loss_term": (c_i, [ctypes.POINTER(MpfUpsampleArgs), c_p]),
+    "mpf_upflow8_loss_term_backward": (c_i, [ctypes.POINTER(MpfUpsampleArgs), c_p]),
     "mpf_gru_reset": (c_i, [ctypes.POINTER(MpfGruArgs), c_p]),
     "mpf_gru_update": (c_i, [ctypes.POINTER(MpfGruArgs), c_p]),
     "mpf_gru_update_backward": (c_i, [ctypes.POINTER(MpfGruArgs), c_p]),

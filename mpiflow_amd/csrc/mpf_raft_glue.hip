@@ -22,6 +22,7 @@
 // No address depends on a tensor's values: NaN and inf travel through the arithmetic as in torch.
 #include "mpf_common.h"
 #include "mpf_math.h"
+#include "mpf_upflow8.h"        // up8_taps, up8_range, up8_weight: shared with the fused bilinear loss of mpf_upsample.hip
 
 #define GLUE_THREADS 256
 #define GLUE_MAX_BLOCKS 2048
@@ -90,15 +91,6 @@ struct Up8Dev {
     unsigned total;
 };
 
-// source index pair and weight of fine index I along an axis of coarse size n: ATen's area_pixel_compute_source_index with align_corners
-__device__ __forceinline__ void up8_taps(int I, int n, float s, int &i0, int &i1, float &l)
-{
-    const float src = s * (float)I;
-    i0 = min((int)src, n - 1);                                            // the product rounds to n-1 at most; the min only guards the bound
-    i1 = i0 + (i0 < n - 1 ? 1 : 0);
-    l = src - (float)i0;
-}
-
 template <int VEC>
 __global__ __launch_bounds__(GLUE_THREADS) void k_upflow8(const Up8Dev a)
 {
@@ -124,27 +116,6 @@ __global__ __launch_bounds__(GLUE_THREADS) void k_upflow8(const Up8Dev a)
         }
         mpf_store_vec<VEC>(a.out + (size_t)row * W8 + X, o);
     }
-}
-
-// the fine indices that can touch coarse index i: those whose source coordinate lies in (i-1, i+1), with a margin of one fine index per side
-// for the roundings (a coordinate is good to a few 1e-5 of a coarse pixel, a fine index is about 1/8 of one); every candidate is tested
-__device__ __forceinline__ void up8_range(int i, int n, int &lo, int &hi)
-{
-    const int n8 = 8 * n;
-    lo = 0, hi = n8 - 1;
-    if (n == 1) return;                                                   // scale 0: every fine index reads coarse index 0
-    const float inv = (float)(n8 - 1) / (float)(n - 1);
-    lo = max(lo, (int)floorf((float)(i - 1) * inv) - 1);
-    hi = min(hi, (int)ceilf((float)(i + 1) * inv) + 1);
-}
-
-// the weight with which fine index I reads coarse index i: the adjoint of up8_taps' two taps (both, where i0 == i1 at the last index)
-__device__ __forceinline__ float up8_weight(int I, int i, int n, float s)
-{
-    int i0, i1;
-    float l;
-    up8_taps(I, n, s, i0, i1, l);
-    return (i0 == i ? 1.0f - l : 0.0f) + (i1 == i ? l : 0.0f);
 }
 
 __global__ __launch_bounds__(GLUE_THREADS) void k_upflow8_bwd(const Up8Dev a)
@@ -242,8 +213,7 @@ static int up8_dev(const MpfRaftGlueArgs *a, const char *who, const float *in, f
     if (rc) return rc;
     MPF_REQUIRE(in && out, "%s: null pointer", who);
     d.in = in, d.out = out, d.H = a->H, d.W = a->W;
-    d.sy = a->H > 1 ? (float)(a->H - 1) / (float)(8 * a->H - 1) : 0.0f;
-    d.sx = a->W > 1 ? (float)(a->W - 1) / (float)(8 * a->W - 1) : 0.0f;
+    d.sy = up8_scale(a->H), d.sx = up8_scale(a->W);
     return 0;
 }
 

@@ -22,12 +22,25 @@
 //
 // No address depends on a tensor's values: NaN and inf travel through the arithmetic as they do in torch (fmaxf drops a NaN from the maximum,
 // but the NaN's own exponential poisons the softmax sum all the same; 0 * inf and inf - inf give the NaN torch gives).
+//
+// The small model has no mask: its prediction is upflow8, 8 x bilinear with align_corners=True (mpf_raft_glue.hip).  The same loss term for it:
+//
+// k_up8_loss               a lane owns 4 consecutive fine pixels of one row: three float4 loads (flow_gt u, v; valid), the prediction formed in
+//                          registers from the 64 x smaller coarse map (cache) with k_upflow8's own expression (mpf_upflow8.h), compared and summed as
+//                          UP_LOSS does; grid-stride over at most UP8_MAX_BLOCKS blocks, one partial row per block, folded by k_upsample_finish.
+// k_up8_loss_bwd           a gather: UP8_GROUP = 32 lanes per COARSE pixel (both channels).  The lanes take consecutive fine columns of the
+//                          pixel's footprint (up8_range; one coalesced run per row) and walk its rows; each candidate's prediction and cotangent
+//                          g / count * v * sign(pred - flow_gt) are formed in registers and weighted with up8_weight.  A lane sums its column in
+//                          fp64 in row order, the 32 lanes fold in a fixed butterfly: no atomics, no workspace, bit-identical from run to run.
 #include "mpf_common.h"
+#include "mpf_upflow8.h"
 
 #define UP_THREADS 256
 #define UP_WAVES 4
 #define UP_ROWS 2                // sub-rows per wave: UP_WAVES * UP_ROWS = 8
 #define UP_NPART 6               // partials per block: S, sum epe, n(epe < 1), n(epe < 3), n(epe < 5), n(v)
+#define UP8_MAX_BLOCKS 4096      // k_up8_loss: grid-stride beyond this many blocks
+#define UP8_GROUP 32             // k_up8_loss_bwd: lanes per coarse pixel
 
 enum { UP_FWD = 0, UP_BWD = 1, UP_LOSS = 2, UP_LOSS_BWD = 3 };
 
@@ -257,6 +270,130 @@ __global__ __launch_bounds__(UP_THREADS) void k_upsample_finish(const UpDev a, i
     }
 }
 
+// the bilinear loss: what the kernels need beyond UpDev
+struct Up8Geo {
+    float sy, sx;                // up8_scale(H), up8_scale(W)
+    unsigned total;              // k_up8_loss: lanes = N * 8H * 2W; k_up8_loss_bwd: coarse pixels = N * H * W
+};
+
+// 8 * bilinear at fine (Y, X) from the two coarse rows r0, r1: k_upflow8's expression, operation for operation
+__device__ __forceinline__ float up8_value(const float *r0, const float *r1, int x0, int x1, float hy, float ly, float hx, float lx)
+{
+    return 8.0f * (hy * (hx * r0[x0] + lx * r0[x1]) + ly * (hx * r1[x0] + lx * r1[x1]));
+}
+
+__global__ __launch_bounds__(UP_THREADS) void k_up8_loss(const UpDev a, const Up8Geo q)
+{
+    __shared__ double sP[UP_WAVES * UP_NPART];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int H = a.H, W = a.W, H8 = 8 * H, W8 = 8 * W;
+    const unsigned per_row = (unsigned)(2 * W);
+    const size_t plane = (size_t)H8 * W8;
+    double S = 0.0, esum = 0.0;
+    int n1 = 0, n3 = 0, n5 = 0, nv = 0;
+    // t < total < 2^29 and the stride is at most UP8_MAX_BLOCKS * UP_THREADS = 2^20, so the last increment cannot wrap
+    for (unsigned t = blockIdx.x * UP_THREADS + threadIdx.x; t < q.total; t += gridDim.x * UP_THREADS) {
+        const unsigned row = t / per_row;                                 // n * 8H + Y
+        const int X = (int)(t - row * per_row) * 4;
+        const int n = (int)(row / (unsigned)H8), Y = (int)(row - (unsigned)n * H8);
+        int y0, y1;
+        float ly;
+        up8_taps(Y, H, q.sy, y0, y1, ly);
+        const float hy = 1.0f - ly;
+        const float *u0 = a.flow + ((size_t)(n * 2) * H + y0) * W, *u1 = a.flow + ((size_t)(n * 2) * H + y1) * W;
+        const float *v0 = u0 + a.HW, *v1 = u1 + a.HW;
+        const float *gsrc = a.flow_gt + ((size_t)(n * 2) * H8 + Y) * W8 + X;
+        const float4 qu = *(const float4 *)gsrc, qv = *(const float4 *)(gsrc + plane), qa = *(const float4 *)(a.valid + (size_t)row * W8 + X);
+        const float gu4[4] = {qu.x, qu.y, qu.z, qu.w}, gv4[4] = {qv.x, qv.y, qv.z, qv.w}, val[4] = {qa.x, qa.y, qa.z, qa.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            int x0, x1;
+            float lx;
+            up8_taps(X + e, W, q.sx, x0, x1, lx);
+            const float hx = 1.0f - lx;
+            const float o0 = up8_value(u0, u1, x0, x1, hy, ly, hx, lx), o1 = up8_value(v0, v1, x0, x1, hy, ly, hx, lx);
+            const float gu = gu4[e], gv = gv4[e];
+            const bool v = val[e] >= 0.5f && sqrtf(gu * gu + gv * gv) < a.max_flow;
+            const float vf = v ? 1.0f : 0.0f;
+            const float d0 = o0 - gu, d1 = o1 - gv;
+            S += (double)(vf * fabsf(d0)) + (double)(vf * fabsf(d1));
+            if (a.metrics && v) {
+                const float epe = sqrtf(d0 * d0 + d1 * d1);
+                esum += (double)epe;
+                n1 += epe < 1.0f, n3 += epe < 3.0f, n5 += epe < 5.0f, nv += 1;
+            }
+        }
+    }
+    double part[UP_NPART] = {S, esum, (double)n1, (double)n3, (double)n5, (double)nv};
+    const int nq = a.metrics ? UP_NPART : 1;
+    for (int k = 0; k < nq; ++k) {
+        const double v = up_wave_sum(part[k]);
+        if (lane == 0) sP[wave * UP_NPART + k] = v;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nq) {
+        double v = sP[threadIdx.x];
+#pragma unroll
+        for (int k = 1; k < UP_WAVES; ++k) v += sP[k * UP_NPART + threadIdx.x];
+        a.partials[(size_t)blockIdx.x * UP_NPART + threadIdx.x] = v;
+    }
+}
+
+__global__ __launch_bounds__(UP_THREADS) void k_up8_loss_bwd(const UpDev a, const Up8Geo q)
+{
+    const int sub = threadIdx.x & (UP8_GROUP - 1);
+    const unsigned pix = blockIdx.x * (UP_THREADS / UP8_GROUP) + (threadIdx.x / UP8_GROUP);
+    const bool live = pix < q.total;
+    const unsigned p = live ? pix : q.total - 1;                          // a group past the end works on the last pixel and stores nothing
+    const int H = a.H, W = a.W, HW = a.HW, H8 = 8 * H, W8 = 8 * W;
+    const int n = (int)(p / (unsigned)HW), yx = (int)(p - (unsigned)n * HW);
+    const int y = yx / W, x = yx - y * W;
+    int ylo, yhi, xlo, xhi;
+    up8_range(y, H, ylo, yhi);
+    up8_range(x, W, xlo, xhi);
+    const float gs = a.g[0] / (float)((long long)a.N * 128 * HW);        // the mean's share of the upstream gradient
+    const float *fu = a.flow + (size_t)(n * 2) * HW, *fv = fu + HW;
+    const size_t plane = (size_t)H8 * W8;
+    const float *gt = a.flow_gt + (size_t)(n * 2) * plane, *va = a.valid + (size_t)n * plane;
+    double acc0 = 0.0, acc1 = 0.0;
+    for (int X = xlo + sub; X <= xhi; X += UP8_GROUP) {
+        const float wx = up8_weight(X, x, W, q.sx);
+        if (wx == 0.0f) continue;
+        int x0, x1;
+        float lx;
+        up8_taps(X, W, q.sx, x0, x1, lx);
+        const float hx = 1.0f - lx;
+        for (int Y = ylo; Y <= yhi; ++Y) {
+            const float wy = up8_weight(Y, y, H, q.sy);
+            if (wy == 0.0f) continue;
+            int y0, y1;
+            float ly;
+            up8_taps(Y, H, q.sy, y0, y1, ly);
+            const float hy = 1.0f - ly;
+            const float o0 = up8_value(fu + y0 * W, fu + y1 * W, x0, x1, hy, ly, hx, lx);
+            const float o1 = up8_value(fv + y0 * W, fv + y1 * W, x0, x1, hy, ly, hx, lx);
+            const size_t at = (size_t)Y * W8 + X;
+            const float gu = gt[at], gv = gt[plane + at];
+            const bool v = va[at] >= 0.5f && sqrtf(gu * gu + gv * gv) < a.max_flow;
+            const float d0 = o0 - gu, d1 = o1 - gv;
+            const float gv_ = gs * (v ? 1.0f : 0.0f);                     // sign(0) = 0, and a NaN difference has sign 0 as torch's sgn has
+            const float c0 = gv_ * (float)((d0 > 0.0f) - (d0 < 0.0f)), c1 = gv_ * (float)((d1 > 0.0f) - (d1 < 0.0f));
+            const double w = (double)wy * (double)wx;                     // exact
+            acc0 += w * (double)c0;
+            acc1 += w * (double)c1;
+        }
+    }
+#pragma unroll
+    for (int m = UP8_GROUP / 2; m >= 1; m >>= 1) {
+        acc0 += __shfl_xor(acc0, m);
+        acc1 += __shfl_xor(acc1, m);
+    }
+    if (live && sub == 0) {
+        a.grad_flow[(size_t)(n * 2) * HW + yx] = (float)(8.0 * acc0);
+        a.grad_flow[(size_t)(n * 2 + 1) * HW + yx] = (float)(8.0 * acc1);
+    }
+}
+
 static size_t up_partials_bytes(int64_t blocks) { return (size_t)blocks * UP_NPART * sizeof(double); }
 
 static int up_shape(int N, int H, int W, const char *who, int64_t &blocks)
@@ -343,4 +480,78 @@ extern "C" int mpf_flow_loss_term(const MpfUpsampleArgs *a, void *stream) { retu
 extern "C" int mpf_flow_loss_term_backward(const MpfUpsampleArgs *a, void *stream)
 {
     return up_launch<UP_LOSS_BWD>(a, stream, "mpf_flow_loss_term_backward");
+}
+
+// the bilinear loss: N, H, W >= 1 and flow_gt [N,2,8H,8W] below 2^31 elements; blocks of k_up8_loss (one partial row each)
+static int up8_loss_shape(int N, int H, int W, const char *who, int64_t &blocks)
+{
+    MPF_REQUIRE(N >= 1 && H >= 1 && W >= 1, "%s: bad shape N, H, W = %d, %d, %d", who, N, H, W);
+    const int64_t lim = (int64_t)1 << 31;
+    const int64_t hw = (int64_t)H * W;
+    MPF_REQUIRE(hw < lim / 128 && (int64_t)N * hw < lim / 128, "%s: flow_gt [N,2,8H,8W] must hold fewer than 2^31 elements (N, H, W = %d, %d, %d)", who, N, H, W);
+    blocks = ((int64_t)N * hw * 16 + UP_THREADS - 1) / UP_THREADS;
+    if (blocks > UP8_MAX_BLOCKS) blocks = UP8_MAX_BLOCKS;
+    return 0;
+}
+
+extern "C" size_t mpf_upflow8_loss_workspace(int N, int H, int W, int backward)
+{
+    int64_t blocks;
+    if (up8_loss_shape(N, H, W, "mpf_upflow8_loss_workspace", blocks)) return 0;
+    return backward ? 0 : up_partials_bytes(blocks);                      // the backward call is a gather: no workspace
+}
+
+static int up8_loss_check(const MpfUpsampleArgs *a, bool backward, const char *who, UpDev &d, Up8Geo &q, int64_t &blocks)
+{
+    MPF_REQUIRE(a, "%s: null argument block", who);
+    MPF_REQUIRE(a->flow, "%s: null pointer (flow)", who);
+    const int rc = up8_loss_shape(a->N, a->H, a->W, who, blocks);
+    if (rc) return rc;
+    MPF_REQUIRE(a->flow_gt && a->valid, "%s: null pointer (flow_gt or valid)", who);
+    MPF_REQUIRE(mpf_aligned16(a->flow_gt) && mpf_aligned16(a->valid), "%s: flow_gt and valid must be 16-byte aligned", who);
+    if (!backward) {
+        MPF_REQUIRE(a->term, "%s: null pointer (term)", who);
+        MPF_REQUIRE(a->workspace, "%s: null pointer (workspace)", who);
+        MPF_REQUIRE((((uintptr_t)a->workspace) & 7) == 0, "%s: workspace must be 8-byte aligned", who);
+        MPF_REQUIRE(a->workspace_bytes >= up_partials_bytes(blocks), "%s: workspace holds %zu bytes, %zu needed (mpf_upflow8_loss_workspace)", who,
+                    a->workspace_bytes, up_partials_bytes(blocks));
+    } else {
+        MPF_REQUIRE(a->g, "%s: null pointer (g)", who);
+        MPF_REQUIRE(a->grad_flow, "%s: null pointer (grad_flow)", who);
+    }
+    d = UpDev{};
+    d.flow = a->flow, d.flow_gt = a->flow_gt, d.valid = a->valid, d.g = a->g, d.grad_flow = a->grad_flow, d.term = a->term;
+    d.metrics = backward ? nullptr : a->metrics;
+    d.partials = backward ? nullptr : (double *)a->workspace;
+    d.N = a->N, d.H = a->H, d.W = a->W, d.HW = a->H * a->W;
+    d.max_flow = a->max_flow;
+    q.sy = up8_scale(a->H), q.sx = up8_scale(a->W);
+    q.total = (unsigned)((int64_t)a->N * d.HW * (backward ? 1 : 16));
+    return 0;
+}
+
+extern "C" int mpf_upflow8_loss_term(const MpfUpsampleArgs *a, void *stream)
+{
+    UpDev d;
+    Up8Geo q;
+    int64_t blocks;
+    const int rc = up8_loss_check(a, false, "mpf_upflow8_loss_term", d, q, blocks);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_up8_loss, dim3((unsigned)blocks), dim3(UP_THREADS), 0, (hipStream_t)stream, d, q);
+    const int st = mpf_launch_status("k_up8_loss");
+    if (st) return st;
+    hipLaunchKernelGGL(k_upsample_finish, dim3(1), dim3(UP_THREADS), 0, (hipStream_t)stream, d, (int)blocks);
+    return mpf_launch_status("k_upsample_finish");
+}
+
+extern "C" int mpf_upflow8_loss_term_backward(const MpfUpsampleArgs *a, void *stream)
+{
+    UpDev d;
+    Up8Geo q;
+    int64_t blocks;
+    const int rc = up8_loss_check(a, true, "mpf_upflow8_loss_term_backward", d, q, blocks);
+    if (rc) return rc;
+    const unsigned per = UP_THREADS / UP8_GROUP;
+    hipLaunchKernelGGL(k_up8_loss_bwd, dim3((q.total + per - 1) / per), dim3(UP_THREADS), 0, (hipStream_t)stream, d, q);
+    return mpf_launch_status("k_up8_loss_bwd");
 }

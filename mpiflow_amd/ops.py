@@ -910,6 +910,49 @@ def flow_loss_term_backward(flow, mask, flow_gt, valid, g, max_flow=400):
     return gf, gm
 
 
+def _up8_loss_args(flow, flow_gt, valid, max_flow, who, **more):
+    """MpfUpsampleArgs of the bilinear loss calls: flow [N,2,H,W], flow_gt [N,2,8H,8W], valid [N,8H,8W]; mask and grad_mask stay NULL"""
+    f = check_tensor(flow, "flow", who, (None, 2, None, None))
+    N, _, H, W = f.shape
+    gt = check_tensor(flow_gt, "flow_gt", who, (N, 2, 8 * H, 8 * W))
+    va = check_tensor(valid, "valid", who, (N, 8 * H, 8 * W))
+    check_devices(who, dict(flow=f, flow_gt=gt, valid=va, **more))
+    a = _lib.MpfUpsampleArgs()
+    a.flow, a.N, a.H, a.W = f.data_ptr(), N, H, W
+    a.flow_gt, a.valid, a.max_flow = gt.data_ptr(), va.data_ptr(), float(max_flow)
+    return a
+
+
+@_on_device
+def upflow8_loss_term(flow, flow_gt, valid, max_flow=400, metrics=False):
+    """mpf_upflow8_loss_term: (v * |upflow8(flow) - flow_gt|).mean() as a 0-d device tensor without forming the prediction (the small model's
+    loss term); v = (valid >= 0.5) & (|flow_gt| < max_flow).  flow [N,2,H,W], flow_gt [N,2,8H,8W], valid [N,8H,8W].  With metrics=True also the
+    five float64 accumulators of flow_loss_term.  -> (term, accumulators or None).  Asynchronous on the current stream."""
+    a = _up8_loss_args(flow, flow_gt, valid, max_flow, "upflow8_loss_term")
+    lib = _lib.load()
+    term = torch.empty((), dtype=_f32, device=flow.device)
+    acc = torch.empty(5, dtype=torch.float64, device=flow.device) if metrics else None
+    ws = torch.empty(int(lib.mpf_upflow8_loss_workspace(a.N, a.H, a.W, 0)) // 8, dtype=torch.float64, device=flow.device)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 8
+    a.term, a.metrics = term.data_ptr(), (acc.data_ptr() if metrics else None)
+    _lib.check(lib.mpf_upflow8_loss_term(ctypes.byref(a), _stream()), "mpf_upflow8_loss_term")
+    del ws
+    return term, acc
+
+
+@_on_device
+def upflow8_loss_term_backward(flow, flow_gt, valid, g, max_flow=400):
+    """mpf_upflow8_loss_term_backward: g, a float32 scalar ON THE DEVICE (the gradient reaching the term; the kernel reads it, the host does
+    not) -> grad_flow [N,2,H,W] of upflow8_loss_term.  The prediction is recomputed; a gather, no atomics, no workspace: bit-identical from
+    run to run.  Asynchronous on the current stream."""
+    g = check_tensor(g, "g", "upflow8_loss_term_backward", ())
+    a = _up8_loss_args(flow, flow_gt, valid, max_flow, "upflow8_loss_term_backward", g=g)
+    gf = torch.empty_like(flow)
+    a.g, a.grad_flow = g.data_ptr(), gf.data_ptr()
+    _lib.check(_lib.load().mpf_upflow8_loss_term_backward(ctypes.byref(a), _stream()), "mpf_upflow8_loss_term_backward")
+    return gf
+
+
 def _gru_slices(dst, terms, name, who, h, limit, tensors):
     """terms: (tensor [B,channels,H,W], channel offset) pairs or None (absent) -> fills the MpfGruTerm array `dst`, adds the tensors by name
     to `tensors` (for the device check that ends the call), returns the count"""

@@ -16,8 +16,9 @@ first half cnet consumes (mpf_raft_images; no cat); tanh / relu of the context n
 gradient is written as one tensor (mpf_context_split); the small model upsamples with mpf_upflow8, a gather in backward.  The per-iteration
 coords1 - coords0 and coords1 + delta_flow stay torch's.  (2) forward takes one more keyword: coarse=True (basic model, not test_mode) returns
 per iteration the pair (coords1 - coords0, up_mask) instead of the upsampled prediction - what raft_upsample.sequence_loss takes, which then
-never writes a full-resolution prediction.  (3) In test_mode only the last iteration is upsampled (the others' upsampled flows are dropped
-upstream too).  (4) Refused instead of computed: mixed_precision=True (the modules are float32 only); frames whose sides are not multiples of
+never writes a full-resolution prediction; coarse="flow" (small model, not test_mode) returns per iteration coords1 - coords0 [N,2,H/8,W/8]
+alone and upsamples nothing - what raft_upsample.sequence_loss(flows, None, ...) takes, which forms upflow8's prediction in registers.
+(3) In test_mode only the last iteration is upsampled (the others' upsampled flows are dropped upstream too).  (4) Refused instead of computed: mixed_precision=True (the modules are float32 only); frames whose sides are not multiples of
 8 (upstream pads them first: utils.InputPadder) or are below 8 * 2^corr_levels = 128 (there the reference's sampler divides by zero at the
 coarsest level and every prediction is NaN).
 
@@ -66,7 +67,7 @@ def coords_grid(batch, ht, wd, device):
 class RAFT(nn.Module):
     """RAFT/core/raft.py's RAFT: RAFT(args)(image1, image2, iters=12, flow_init=None, upsample=True, test_mode=False) -> the list of
     upsampled predictions [N,2,H,W], or in test_mode (coords1 - coords0, flow_up).  image1, image2 [N,3,H,W] float32 in 0..255 on the GPU, H and
-    W multiples of 8 and at least 128; flow_init [N,2,H/8,W/8].  coarse=True: see the module docstring."""
+    W multiples of 8 and at least 128; flow_init [N,2,H/8,W/8].  coarse=True (basic) / coarse="flow" (small): see the module docstring."""
 
     def __init__(self, args):
         super().__init__()
@@ -138,10 +139,15 @@ class RAFT(nn.Module):
         tensors = dict(image1=image1, image2=image2)
         if flow_init is not None:
             tensors["flow_init"] = check_tensor(contiguous(flow_init), "flow_init", who, (N, 2, H // 8, W // 8), "[N,2,H/8,W/8]")
-        if coarse and self.args.small:
-            raise MpiFlowHipError("%s: coarse=True needs the basic model: the small one has no upsampling mask to hand to sequence_loss" % who)
+        if not isinstance(coarse, bool) and not (isinstance(coarse, str) and coarse == "flow"):
+            raise MpiFlowHipError("%s: coarse must be False, True or \"flow\" (got %r)" % (who, coarse))
+        if coarse is True and self.args.small:
+            raise MpiFlowHipError("%s: coarse=True needs the basic model: the small one has no upsampling mask to hand to sequence_loss; "
+                                  "coarse=\"flow\" returns its coarse flows for sequence_loss(flows, None, ...)" % who)
+        if coarse == "flow" and not self.args.small:
+            raise MpiFlowHipError("%s: coarse=\"flow\" is the small model's: the basic one has an upsampling mask, use coarse=True" % who)
         if coarse and test_mode:
-            raise MpiFlowHipError("%s: coarse=True returns the training list; it cannot be combined with test_mode=True" % who)
+            raise MpiFlowHipError("%s: coarse=%s returns the training list; it cannot be combined with test_mode=True" % (who, "True" if coarse is True else '"flow"'))
         check_devices(who, tensors)
         return image1, image2, tensors.get("flow_init")
 
@@ -174,7 +180,7 @@ class RAFT(nn.Module):
             net, up_mask, delta_flow = self.update_block(net, inp, corr, flow)
             coords1 = coords1 + delta_flow                      # F(t+1) = F(t) + \Delta(t)
             if coarse:
-                flow_predictions.append((coords1 - coords0, up_mask))
+                flow_predictions.append((coords1 - coords0, up_mask) if coarse is True else coords1 - coords0)
                 continue
             if test_mode and itr < iters - 1:
                 continue

@@ -3,10 +3,14 @@
 the same four modules - the SAME parameters - wired with upstream's torch glue, full-resolution predictions and train.py's loss; in ONE
 process, the forms alternating round by round after a warm-up, every figure the median of the rounds with min and max beside it.
 
-    python tools/bench_raft.py [--rounds 7] [--warmup 2] [--batch 8] [--height 288] [--width 960] [--iters 12] [--out profiles/raft/bench.json]
+    python tools/bench_raft.py [--small] [--rounds 7] [--warmup 2] [--batch 8] [--height 288] [--width 960] [--iters 12] [--out profiles/raft/bench.json]
 
 Per form: forward (grad enabled, as in training: what backward needs is kept) and forward + backward, time and peak allocated memory.  The
-glue is a small share of a step; what coarse=True buys is the memory of the predictions and of what upsampling keeps for backward."""
+glue is a small share of a step; what coarse=True buys is the memory of the predictions and of what upsampling keeps for backward.
+
+--small: the small model.  coarse="flow" feeding sequence_loss(flows, None, ...) (the fused bilinear loss) against the way without it: the
+model's own upflow8 predictions (coarse=False) and train.py's loss in torch.  Same process, same parameters, alternating.  Also the loss
+tail alone, on the coarse flows of one forward pass, detached: tail_fwd and tail_fwd_bwd, the same two forms."""
 import argparse
 import json
 import os
@@ -60,12 +64,13 @@ def main():
     ap.add_argument("--height", type=int, default=288)
     ap.add_argument("--width", type=int, default=960)
     ap.add_argument("--iters", type=int, default=12)
+    ap.add_argument("--small", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_raft.py needs a GPU"
     dev = torch.device("cuda:0")
     torch.manual_seed(1)
-    model = RAFT(argparse.Namespace(small=False, mixed_precision=False)).to(dev).train()
+    model = RAFT(argparse.Namespace(small=a.small, mixed_precision=False)).to(dev).train()
     im1 = torch.randint(0, 256, (a.batch, 3, a.height, a.width), device=dev).float()
     im2 = torch.roll(im1, (2, 5), dims=(2, 3))
     gt = 5.0 * torch.randn(a.batch, 2, a.height, a.width, device=dev)
@@ -78,15 +83,34 @@ def main():
     def torch_glue():
         return torch_sequence_loss(torch_glue_forward(model, im1, im2, a.iters), gt, valid)
 
-    forms = dict(hip_glue_coarse=hip_coarse, torch_glue_full=torch_glue)
+    def small_coarse_flow():
+        return raft_upsample.sequence_loss(model(im1, im2, iters=a.iters, coarse="flow"), None, gt, valid, gamma=0.8)[0]
+
+    def small_upflow8_full():
+        return torch_sequence_loss(model(im1, im2, iters=a.iters), gt, valid)
+
+    groups = {"step": dict(hip_glue_coarse=hip_coarse, torch_glue_full=torch_glue)}
+    if a.small:
+        with torch.no_grad():
+            coarse = [f.clone().requires_grad_(True) for f in model(im1, im2, iters=a.iters, coarse="flow")]
+
+        def clear():
+            for f in coarse:
+                f.grad = None
+
+        groups = {"step": dict(coarse_flow_fused_loss=small_coarse_flow, upflow8_torch_loss=small_upflow8_full),
+                  "tail": dict(coarse_flow_fused_loss=lambda: (clear(), raft_upsample.sequence_loss(coarse, None, gt, valid, gamma=0.8)[0])[1],
+                               upflow8_torch_loss=lambda: (clear(), torch_sequence_loss([raft_upsample.upflow8(f) for f in coarse], gt, valid))[1])}
+    forms = {(g, k): fn for g, d in groups.items() for k, fn in d.items()}
     times = {(k, b): [] for k in forms for b in (False, True)}
-    peak = {}
+    peak, rise = {}, {}                                                  # peak allocated, and its rise above what was held before the call
     for r in range(a.warmup + a.rounds):
         for backward in (False, True):
             for k, fn in forms.items():
                 model.zero_grad(set_to_none=True)
                 torch.cuda.synchronize()
                 torch.cuda.reset_peak_memory_stats(dev)
+                held = torch.cuda.memory_allocated(dev)
                 t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 t0.record()
                 loss = fn()
@@ -98,10 +122,13 @@ def main():
                 if r >= a.warmup:
                     times[(k, backward)].append(t0.elapsed_time(t1))
                     peak[(k, backward)] = max(peak.get((k, backward), 0), torch.cuda.max_memory_allocated(dev))
+                    rise[(k, backward)] = max(rise.get((k, backward), 0), torch.cuda.max_memory_allocated(dev) - held)
     out = []
     for (k, backward), v in times.items():
-        rec = dict(shape="%dx%dx%d" % (a.batch, a.height, a.width), iters=a.iters, measurement="step_fwd_bwd" if backward else "step_fwd", form=k,
-                   ms_median=round(statistics.median(v), 3), ms_min=round(min(v), 3), ms_max=round(max(v), 3), peak_mib=round(peak[(k, backward)] / 2 ** 20, 1))
+        rec = dict(model="small" if a.small else "basic", shape="%dx%dx%d" % (a.batch, a.height, a.width), iters=a.iters,
+                   measurement=k[0] + ("_fwd_bwd" if backward else "_fwd"), form=k[1],
+                   ms_median=round(statistics.median(v), 3), ms_min=round(min(v), 3), ms_max=round(max(v), 3), peak_mib=round(peak[(k, backward)] / 2 ** 20, 1),
+                   rise_mib=round(rise[(k, backward)] / 2 ** 20, 1))
         out.append(rec)
         print(json.dumps(rec))
     if a.out:
