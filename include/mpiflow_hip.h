@@ -42,7 +42,8 @@ extern "C" {
                              their _backward calls with MpfGruTerm / MpfGruArgs, and now mpf_norm_stats, mpf_norm_act, mpf_norm_act_backward_reduce and
                              mpf_norm_act_backward with MpfNormTerm / MpfNormArgs, and now mpf_raft_images, mpf_context_split, mpf_upflow8 and
                              their _backward calls with MpfRaftGlueArgs, and now mpf_upflow8_loss_term, its _backward call and
-                             mpf_upflow8_loss_workspace with MpfUpsampleArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
+                             mpf_upflow8_loss_workspace with MpfUpsampleArgs, and now mpf_raft_images_padded, mpf_upsample_flow_crop, mpf_upflow8_crop,
+                             mpf_flow_metrics and mpf_flow_metrics_workspace with MpfRaftEvalArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
 
 /* d_params layout (floats):
  *   [0..8]   K_src^-1 (3x3 row-major)            [9..20]  G_tgt_src rows 0..2 (3x4 row-major: R | t)
@@ -673,6 +674,46 @@ int mpf_context_split(const MpfRaftGlueArgs *a, void *stream);
 int mpf_context_split_backward(const MpfRaftGlueArgs *a, void *stream);
 int mpf_upflow8(const MpfRaftGlueArgs *a, void *stream);
 int mpf_upflow8_backward(const MpfRaftGlueArgs *a, void *stream);
+
+/* What RAFT/evaluate.py does around the model on frames whose sides are no multiples of 8.  All tensors f32, contiguous.  The pad is
+ * InputPadder's (RAFT/core/utils/utils.py:7-24): pad_left, pad_right, pad_top, pad_bottom, each 0..7.
+ *   mpf_raft_images_padded   image1, image2 [N,3,H,W]; Hp = H + pad_top + pad_bottom and Wp = W + pad_left + pad_right multiples of 8:
+ *                            pair [2N,3,Hp,Wp] <- 2 * (x / 255) - 1 of the replicate-padded images (source indices clamped), image1 first: what
+ *                            mpf_raft_images makes of F.pad(image, pad, mode='replicate'), bit for bit, the padded images never written.  With a
+ *                            pad of zeros it is mpf_raft_images.
+ *   mpf_upsample_flow_crop   flow [N,2,H,W], mask [N,576,H,W] (H, W: the coarse map): flow_up [N,2,8H-pad_top-pad_bottom,8W-pad_left-pad_right]
+ *                            <- rows pad_top .., columns pad_left .. of mpf_upsample_flow's [N,2,8H,8W], bit for bit; that tensor is never
+ *                            written, and mask channels of sub-positions outside the window are not read.
+ *   mpf_upflow8_crop         flow [N,2,H,W]: the same window of mpf_upflow8's result, bit for bit (mask ignored).
+ *   mpf_flow_metrics         flow_pr, flow_gt [N,2,H,W], valid [N,H,W] or NULL (every pixel counts): metrics [N,6] f64 <- per frame, over the
+ *                            pixels with valid >= 0.5: the sum of epe, their number, the numbers with epe < 1, < 3, < 5, and the number of
+ *                            outliers, epe > 3 and epe / mag > 0.05 (validate_kitti; mag = 0 gives inf, an outlier).  epe = sqrt(du^2 + dv^2) and
+ *                            mag = sqrt(gt_u^2 + gt_v^2) in fp32.  No max_flow rule.  Sums in f64, per-block partials folded in a fixed order, no
+ *                            atomics: bit-identical from run to run.  workspace: mpf_flow_metrics_workspace(N, H, W) bytes, 8-byte aligned,
+ *                            contents irrelevant before and after; N <= 65535.
+ * Any sizes >= 1 with every tensor below 2^31 elements; pair must be 16-byte aligned (it is stored 16 bytes at a time), no other f32 tensor
+ * needs any alignment.  Outputs must not overlap inputs.  Tensor VALUES are unrestricted and no value changes an address.  Validated before
+ * anything is launched (MPF_ERR_BAD_ARGUMENT): a NULL block, non-positive sizes, a pad outside 0..7, a padded frame that is no multiple of 8,
+ * a pad that leaves no window, a tensor of 2^31 elements or more, NULL pointers the call uses. */
+typedef struct MpfRaftEvalArgs {
+    const float *image1, *image2;    /* mpf_raft_images_padded: [N,3,H,W] each */
+    float *pair;                     /* mpf_raft_images_padded: [2N,3,Hp,Wp], written */
+    const float *flow;               /* crop calls: [N,2,H,W] */
+    const float *mask;               /* mpf_upsample_flow_crop: [N,576,H,W] */
+    float *flow_up;                  /* crop calls: the window, written */
+    const float *flow_pr, *flow_gt;  /* mpf_flow_metrics: [N,2,H,W] each */
+    const float *valid;              /* mpf_flow_metrics: [N,H,W] or NULL */
+    double *metrics;                 /* mpf_flow_metrics: [N,6], written */
+    void *workspace;                 /* mpf_flow_metrics */
+    size_t workspace_bytes;
+    int N, H, W;                     /* mpf_raft_images_padded: the unpadded frame; crop calls: the coarse (1/8) map; mpf_flow_metrics: the frame */
+    int pad_left, pad_right, pad_top, pad_bottom;
+} MpfRaftEvalArgs;
+int mpf_raft_images_padded(const MpfRaftEvalArgs *a, void *stream);
+int mpf_upsample_flow_crop(const MpfRaftEvalArgs *a, void *stream);
+int mpf_upflow8_crop(const MpfRaftEvalArgs *a, void *stream);
+size_t mpf_flow_metrics_workspace(int N, int H, int W);   /* 0 for a shape the call refuses */
+int mpf_flow_metrics(const MpfRaftEvalArgs *a, void *stream);
 
 /* [3,H,W] float RGB -> [H,W,3] u8 BGR, clip(rint(x*255))  (utils/utils.py:174-177) */
 int mpf_to_u8_bgr(const float *d_img, int H, int W, uint8_t *d_out, void *stream);

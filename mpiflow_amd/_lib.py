@@ -164,6 +164,13 @@ class MpfRaftGlueArgs(ctypes.Structure):
                 ("N", c_i), ("H", c_i), ("W", c_i), ("hdim", c_i), ("cdim", c_i)]
 
 
+class MpfRaftEvalArgs(ctypes.Structure):
+    """struct MpfRaftEvalArgs of include/mpiflow_hip.h: RAFT evaluation on frames of any size: padded image batch, cropped upsampling, metrics."""
+    _fields_ = [("image1", c_p), ("image2", c_p), ("pair", c_p), ("flow", c_p), ("mask", c_p), ("flow_up", c_p), ("flow_pr", c_p), ("flow_gt", c_p),
+                ("valid", c_p), ("metrics", c_p), ("workspace", c_p), ("workspace_bytes", c_sz),
+                ("N", c_i), ("H", c_i), ("W", c_i), ("pad_left", c_i), ("pad_right", c_i), ("pad_top", c_i), ("pad_bottom", c_i)]
+
+
 MAX_VIEWS = 16          # MPF_MAX_VIEWS
 SUPPORT_CELL_W, SUPPORT_CELL_H = 32, 8      # MPF_SUPPORT_CELL_W / _H
 
@@ -233,6 +240,11 @@ SIGNATURES = {
     "mpf_context_split_backward": (c_i, [ctypes.POINTER(MpfRaftGlueArgs), c_p]),
     "mpf_upflow8": (c_i, [ctypes.POINTER(MpfRaftGlueArgs), c_p]),
     "mpf_upflow8_backward": (c_i, [ctypes.POINTER(MpfRaftGlueArgs), c_p]),
+    "mpf_raft_images_padded": (c_i, [ctypes.POINTER(MpfRaftEvalArgs), c_p]),
+    "mpf_upsample_flow_crop": (c_i, [ctypes.POINTER(MpfRaftEvalArgs), c_p]),
+    "mpf_upflow8_crop": (c_i, [ctypes.POINTER(MpfRaftEvalArgs), c_p]),
+    "mpf_flow_metrics_workspace": (c_sz, [c_i, c_i, c_i]),
+    "mpf_flow_metrics": (c_i, [ctypes.POINTER(MpfRaftEvalArgs), c_p]),
     "mpf_src_xyz": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
     "mpf_transform_xyz": (c_i, [c_p, c_p, c_i, c_i64, c_p, c_p]),
     "mpf_homography_sample": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),

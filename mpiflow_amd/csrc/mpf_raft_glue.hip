@@ -22,7 +22,8 @@
 // No address depends on a tensor's values: NaN and inf travel through the arithmetic as in torch.
 #include "mpf_common.h"
 #include "mpf_math.h"
-#include "mpf_upflow8.h"        // up8_taps, up8_range, up8_weight: shared with the fused bilinear loss of mpf_upsample.hip
+#include "mpf_raft_scale.h"     // raft_scale: shared with the padded batch of mpf_raft_eval.hip
+#include "mpf_upflow8.h"        // up8_taps, up8_range, up8_weight, up8_value: shared with the fused bilinear loss of mpf_upsample.hip
 
 #define GLUE_THREADS 256
 #define GLUE_MAX_BLOCKS 2048
@@ -43,7 +44,7 @@ __global__ __launch_bounds__(GLUE_THREADS) void k_raft_images(const float *im1, 
         float v[VEC];
         mpf_load_vec<VEC>(src, v);
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) v[e] = 2.0f * (v[e] / 255.0f) - 1.0f;
+        for (int e = 0; e < VEC; ++e) v[e] = raft_scale(v[e]);
         mpf_store_vec<VEC>(pair + (size_t)t * VEC, v);
     }
 }
@@ -112,7 +113,7 @@ __global__ __launch_bounds__(GLUE_THREADS) void k_upflow8(const Up8Dev a)
             float lx;
             up8_taps(X + e, a.W, a.sx, x0, x1, lx);
             const float hx = 1.0f - lx;
-            o[e] = 8.0f * (hy * (hx * p0[x0] + lx * p0[x1]) + ly * (hx * p1[x0] + lx * p1[x1]));
+            o[e] = up8_value(p0, p1, x0, x1, hy, ly, hx, lx);
         }
         mpf_store_vec<VEC>(a.out + (size_t)row * W8 + X, o);
     }

@@ -1,6 +1,7 @@
 // mpf_upflow8.h - the coordinate arithmetic of RAFT's upflow8 (8 x bilinear, align_corners=True), shared by the kernels that write the
-// upsampled flow (mpf_raft_glue.hip: k_upflow8, k_upflow8_bwd) and by those that only compare it (mpf_upsample.hip: k_up8_loss, k_up8_loss_bwd),
-// so that a prediction formed in registers is the prediction mpf_upflow8 writes, bit for bit.
+// upsampled flow (mpf_raft_glue.hip: k_upflow8, k_upflow8_bwd), by those that only compare it (mpf_upsample.hip: k_up8_loss, k_up8_loss_bwd)
+// and by the one that writes a window of it (mpf_raft_eval.hip: k_upflow8_crop), so that a prediction formed anywhere is the prediction
+// mpf_upflow8 writes, bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -35,4 +36,11 @@ __device__ __forceinline__ float up8_weight(int I, int i, int n, float s)
     float l;
     up8_taps(I, n, s, i0, i1, l);
     return (i0 == i ? 1.0f - l : 0.0f) + (i1 == i ? l : 0.0f);
+}
+
+// 8 * bilinear at one fine pixel from the two coarse rows r0, r1, the taps and weights of up8_taps per axis (hy = 1 - ly, hx = 1 - lx):
+// ATen's upsample_bilinear2d, operation for operation.  Every kernel that forms a prediction of upflow8 forms it here.
+__device__ __forceinline__ float up8_value(const float *r0, const float *r1, int x0, int x1, float hy, float ly, float hx, float lx)
+{
+    return 8.0f * (hy * (hx * r0[x0] + lx * r0[x1]) + ly * (hx * r1[x0] + lx * r1[x1]));
 }

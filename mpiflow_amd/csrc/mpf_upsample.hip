@@ -26,13 +26,14 @@
 // The small model has no mask: its prediction is upflow8, 8 x bilinear with align_corners=True (mpf_raft_glue.hip).  The same loss term for it:
 //
 // k_up8_loss               a lane owns 4 consecutive fine pixels of one row: three float4 loads (flow_gt u, v; valid), the prediction formed in
-//                          registers from the 64 x smaller coarse map (cache) with k_upflow8's own expression (mpf_upflow8.h), compared and summed as
+//                          registers from the 64 x smaller coarse map (cache) with k_upflow8's own expression (up8_value, mpf_upflow8.h), compared and summed as
 //                          UP_LOSS does; grid-stride over at most UP8_MAX_BLOCKS blocks, one partial row per block, folded by k_upsample_finish.
 // k_up8_loss_bwd           a gather: UP8_GROUP = 32 lanes per COARSE pixel (both channels).  The lanes take consecutive fine columns of the
 //                          pixel's footprint (up8_range; one coalesced run per row) and walk its rows; each candidate's prediction and cotangent
 //                          g / count * v * sign(pred - flow_gt) are formed in registers and weighted with up8_weight.  A lane sums its column in
 //                          fp64 in row order, the 32 lanes fold in a fixed butterfly: no atomics, no workspace, bit-identical from run to run.
 #include "mpf_common.h"
+#include "mpf_convex.h"          // up_neighbourhood, up_convex: shared with the cropped upsampling of mpf_raft_eval.hip
 #include "mpf_upflow8.h"
 
 #define UP_THREADS 256
@@ -84,14 +85,7 @@ __global__ __launch_bounds__(UP_THREADS) void k_upsample(const UpDev a)
     const int h = pc / W, w = pc - h * W;
 
     float f[2][9];                                           // 8 * flow on the 3 x 3 neighbourhood, 0 outside the map
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            const int hh = h + k / 3 - 1, ww = w + k % 3 - 1;
-            const bool in = (unsigned)hh < (unsigned)H && (unsigned)ww < (unsigned)W;
-            f[c][k] = in ? 8.0f * a.flow[((n * 2 + c) * H + (in ? hh : h)) * W + (in ? ww : w)] : 0.0f;
-        }
+    up_neighbourhood(a.flow, n, H, W, h, w, f);
 
     float gs = 0.0f;
     if (MODE == UP_LOSS_BWD) gs = a.g[0] / (float)((long long)a.N * 128 * HW);      // the mean's share of the upstream gradient
@@ -129,26 +123,8 @@ __global__ __launch_bounds__(UP_THREADS) void k_upsample(const UpDev a)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int ch0 = (n * 576 + i * 8 + j) * HW + pc;
-            float m[9];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) m[k] = a.mask[ch0 + k * plane];
-            float mx = m[0];
-#pragma unroll
-            for (int k = 1; k < 9; ++k) mx = fmaxf(mx, m[k]);
-            float s = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) {
-                m[k] = expf(m[k] - mx);
-                s += m[k];
-            }
-#pragma unroll
-            for (int k = 0; k < 9; ++k) m[k] = m[k] / s;     // m is now the softmax p[k]
-            float o0 = m[0] * f[0][0], o1 = m[0] * f[1][0];
-#pragma unroll
-            for (int k = 1; k < 9; ++k) {
-                o0 = fmaf(m[k], f[0][k], o0);
-                o1 = fmaf(m[k], f[1][k], o1);
-            }
+            float m[9], o0, o1;
+            up_convex(a.mask + ch0, plane, f, m, o0, o1);    // m is now the softmax p[k]
             o[0][j] = o0, o[1][j] = o1;
 
             float c0 = 0.0f, c1 = 0.0f;                      // the cotangent at this entry
@@ -275,12 +251,6 @@ struct Up8Geo {
     float sy, sx;                // up8_scale(H), up8_scale(W)
     unsigned total;              // k_up8_loss: lanes = N * 8H * 2W; k_up8_loss_bwd: coarse pixels = N * H * W
 };
-
-// 8 * bilinear at fine (Y, X) from the two coarse rows r0, r1: k_upflow8's expression, operation for operation
-__device__ __forceinline__ float up8_value(const float *r0, const float *r1, int x0, int x1, float hy, float ly, float hx, float lx)
-{
-    return 8.0f * (hy * (hx * r0[x0] + lx * r0[x1]) + ly * (hx * r1[x0] + lx * r1[x1]));
-}
 
 __global__ __launch_bounds__(UP_THREADS) void k_up8_loss(const UpDev a, const Up8Geo q)
 {

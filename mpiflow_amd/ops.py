@@ -5,6 +5,7 @@ libmpiflow_hip.so.  Every function launches asynchronously on torch's current st
 the library is missing or a launch fails - there is no eager/CPU fallback.
 """
 import ctypes
+import operator
 
 import torch
 
@@ -1338,6 +1339,104 @@ def upflow8_backward(grad_out):
     a.g_up, a.grad_flow, a.N, a.H, a.W = g.data_ptr(), grad.data_ptr(), N, H8 // 8, W8 // 8
     _lib.check(_lib.load().mpf_upflow8_backward(ctypes.byref(a), _stream()), "mpf_upflow8_backward")
     return grad
+
+
+def _eval_pad(a, pad, who):
+    """InputPadder._pad = (left, right, top, bottom), each 0..7, into an MpfRaftEvalArgs"""
+    try:
+        sides = [operator.index(p) for p in pad]
+    except TypeError:
+        sides = []
+    if len(sides) != 4 or not all(0 <= p <= 7 for p in sides):
+        raise _lib.MpiFlowHipError("%s: pad must be (left, right, top, bottom), four integers 0..7, as InputPadder._pad (got %r)" % (who, pad))
+    a.pad_left, a.pad_right, a.pad_top, a.pad_bottom = sides
+
+
+@_on_device
+def raft_images_padded(image1, image2, pad):
+    """mpf_raft_images_padded: raft_images(F.pad(image1, pad, mode='replicate'), F.pad(image2, ...)) in one launch, bit for bit, without the
+    padded images: [N,3,H,W] twice -> the [2N,3,Hp,Wp] batch RAFT's feature network takes (image1 first).  pad = (left, right, top, bottom),
+    each 0..7 (InputPadder._pad); Hp = H + top + bottom and Wp = W + left + right must be multiples of 8.  float32, contiguous, on the GPU, or
+    MpiFlowHipError.  Asynchronous on the current stream."""
+    who = "raft_images_padded"
+    im1 = check_tensor(image1, "image1", who, (None, 3, None, None))
+    im2 = check_tensor(image2, "image2", who, tuple(im1.shape))
+    a = _lib.MpfRaftEvalArgs()
+    _eval_pad(a, pad, who)
+    N, _, H, W = im1.shape
+    Hp, Wp = H + a.pad_top + a.pad_bottom, W + a.pad_left + a.pad_right
+    if Hp % 8 or Wp % 8:
+        raise _lib.MpiFlowHipError("%s: the padded frame's H and W must be multiples of 8 (%d x %d with pad %s is %d x %d)" % (who, H, W, tuple(pad), Hp, Wp))
+    check_devices(who, dict(image1=im1, image2=im2))
+    pair = torch.empty((2 * N, 3, Hp, Wp), dtype=_f32, device=im1.device)
+    a.image1, a.image2, a.pair, a.N, a.H, a.W = im1.data_ptr(), im2.data_ptr(), pair.data_ptr(), N, H, W
+    _lib.check(_lib.load().mpf_raft_images_padded(ctypes.byref(a), _stream()), "mpf_raft_images_padded")
+    return pair
+
+
+def _crop_args(flow, mask, pad, out, who):
+    """MpfRaftEvalArgs of the two cropped upsamplings and the window they write (`out`, or a new tensor); mask None: the bilinear one"""
+    f = check_tensor(flow, "flow", who, (None, 2, None, None))
+    N, _, H, W = f.shape
+    tensors = dict(flow=f)
+    if mask is not None:
+        tensors["mask"] = check_tensor(mask, "mask", who, (N, 576, H, W))
+    a = _lib.MpfRaftEvalArgs()
+    _eval_pad(a, pad, who)
+    Ho, Wo = 8 * H - a.pad_top - a.pad_bottom, 8 * W - a.pad_left - a.pad_right
+    if Ho < 1 or Wo < 1:
+        raise _lib.MpiFlowHipError("%s: pad %s leaves no window of the %d x %d prediction" % (who, tuple(pad), 8 * H, 8 * W))
+    if out is not None:
+        tensors["out"] = check_tensor(out, "out", who, (N, 2, Ho, Wo), "[N,2,8H-top-bottom,8W-left-right]")
+    check_devices(who, tensors)
+    if out is None:
+        out = torch.empty((N, 2, Ho, Wo), dtype=_f32, device=f.device)
+    a.flow, a.mask, a.flow_up, a.N, a.H, a.W = f.data_ptr(), (mask.data_ptr() if mask is not None else None), out.data_ptr(), N, H, W
+    return a, out
+
+
+@_on_device
+def upsample_flow_crop(flow, mask, pad, out=None):
+    """mpf_upsample_flow_crop: InputPadder.unpad(upsample_flow(flow, mask)) without the padded prediction, bit for bit: flow [N,2,H,W], mask
+    [N,576,H,W], pad = (left, right, top, bottom), each 0..7 -> [N,2,8H-top-bottom,8W-left-right].  Mask channels of sub-positions outside the
+    window are not read.  `out`: a contiguous tensor of that shape to write (any alignment).  Asynchronous on the current stream."""
+    a, out = _crop_args(flow, mask, pad, out, "upsample_flow_crop")
+    _lib.check(_lib.load().mpf_upsample_flow_crop(ctypes.byref(a), _stream()), "mpf_upsample_flow_crop")
+    return out
+
+
+@_on_device
+def upflow8_crop(flow, pad, out=None):
+    """mpf_upflow8_crop: InputPadder.unpad(upflow8(flow)) without the padded prediction, bit for bit (the small model's upsampling): flow
+    [N,2,H,W], pad = (left, right, top, bottom), each 0..7 -> [N,2,8H-top-bottom,8W-left-right].  Asynchronous on the current stream."""
+    a, out = _crop_args(flow, None, pad, out, "upflow8_crop")
+    _lib.check(_lib.load().mpf_upflow8_crop(ctypes.byref(a), _stream()), "mpf_upflow8_crop")
+    return out
+
+
+@_on_device
+def flow_metrics(flow_pr, flow_gt, valid=None):
+    """mpf_flow_metrics: evaluate.py's per-frame sums in one launch pair: flow_pr, flow_gt [N,2,H,W], valid [N,H,W] or None (every pixel counts)
+    -> a float64 device tensor [N,6]: per frame, over the pixels with valid >= 0.5, the sum of epe, their number, the numbers with epe < 1, < 3,
+    < 5 and the number of outliers (epe > 3 and epe / |flow_gt| > 0.05).  No max_flow rule.  Bit-identical from run to run.  Asynchronous on the
+    current stream: no host copy, no synchronisation."""
+    who = "flow_metrics"
+    pr = check_tensor(flow_pr, "flow_pr", who, (None, 2, None, None))
+    N, _, H, W = pr.shape
+    gt = check_tensor(flow_gt, "flow_gt", who, (N, 2, H, W))
+    tensors = dict(flow_pr=pr, flow_gt=gt)
+    if valid is not None:
+        tensors["valid"] = check_tensor(valid, "valid", who, (N, H, W))
+    check_devices(who, tensors)
+    lib = _lib.load()
+    acc = torch.empty((N, 6), dtype=torch.float64, device=pr.device)
+    ws = torch.empty(int(lib.mpf_flow_metrics_workspace(N, H, W)) // 8, dtype=torch.float64, device=pr.device)
+    a = _lib.MpfRaftEvalArgs()
+    a.flow_pr, a.flow_gt, a.valid, a.metrics, a.N, a.H, a.W = pr.data_ptr(), gt.data_ptr(), (valid.data_ptr() if valid is not None else None), acc.data_ptr(), N, H, W
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 8
+    _lib.check(lib.mpf_flow_metrics(ctypes.byref(a), _stream()), "mpf_flow_metrics")
+    del ws
+    return acc
 
 
 @_on_device

@@ -22,6 +22,9 @@ alone and upsamples nothing - what raft_upsample.sequence_loss(flows, None, ...)
 8 (upstream pads them first: utils.InputPadder) or are below 8 * 2^corr_levels = 128 (there the reference's sampler divides by zero at the
 coarsest level and every prediction is NaN).
 
+Beside forward: predict(image1, image2, iters=12, flow_init=None, mode='sintel') is evaluate.py's pad / forward(test_mode=True) / unpad for
+frames of any size, with the padding fused into the image scaling and the last prediction written as its unpadded window (raft_eval.py).
+
 Limits: the contract of _tensors.py: float32 images on the GPU, checked in its order (type, dtype, shape, what the call
 requires, the device last); non-contiguous images are made contiguous, as upstream does.  No CPU path, no eager fallback: MpiFlowHipError.
 """
@@ -32,6 +35,7 @@ from . import ops
 from ._lib import MpiFlowHipError
 from ._tensors import check_devices, check_tensor
 from .raft_corr import AlternateCorrBlock, CorrBlock
+from .raft_eval import InputPadder
 from .raft_extractor import BasicEncoder, SmallEncoder
 from .raft_update import BasicUpdateBlock, SmallUpdateBlock
 from .raft_upsample import upflow8, upsample_flow
@@ -154,10 +158,15 @@ class RAFT(nn.Module):
     def forward(self, image1, image2, iters=12, flow_init=None, upsample=True, test_mode=False, coarse=False):
         """Estimate optical flow between pair of frames"""
         image1, image2, flow_init = self._check(image1, image2, flow_init, test_mode, coarse)
-        N = image1.shape[0]
+        pair = ops.raft_images(image1, image2)                  # [2N,3,H,W]: 2 * (x / 255) - 1, image1 first
+        return self._refine(pair, iters, flow_init, test_mode, coarse)
+
+    def _refine(self, pair, iters, flow_init, test_mode, coarse, crop=None):
+        """forward from the prepared batch on: pair [2N,3,H,W], H and W multiples of 8.  crop (test_mode only): InputPadder._pad; the last
+        prediction is then written as its unpadded window alone (ops.upsample_flow_crop / ops.upflow8_crop)."""
+        N = pair.shape[0] // 2
         hdim = self.hidden_dim
 
-        pair = ops.raft_images(image1, image2)                  # [2N,3,H,W]: 2 * (x / 255) - 1, image1 first
         fmaps = self.fnet(pair)
         fmap1, fmap2 = fmaps[:N], fmaps[N:]
         if self.args.alternate_corr:
@@ -167,7 +176,7 @@ class RAFT(nn.Module):
 
         net, inp = context_split(self.cnet(pair[:N]), hdim)
 
-        coords0, coords1 = self.initialize_flow(image1)
+        coords0, coords1 = self.initialize_flow(pair[:N])
         if flow_init is not None:
             coords1 = coords1 + flow_init
 
@@ -184,7 +193,9 @@ class RAFT(nn.Module):
                 continue
             if test_mode and itr < iters - 1:
                 continue
-            if up_mask is None:
+            if crop is not None:
+                flow_up = ops.upflow8_crop(coords1 - coords0, crop) if up_mask is None else ops.upsample_flow_crop(coords1 - coords0, up_mask.contiguous(), crop)
+            elif up_mask is None:
                 flow_up = upflow8(coords1 - coords0)
             else:
                 flow_up = self.upsample_flow(coords1 - coords0, up_mask)
@@ -193,3 +204,30 @@ class RAFT(nn.Module):
         if test_mode:
             return coords1 - coords0, flow_up
         return flow_predictions
+
+    @torch.no_grad()
+    def predict(self, image1, image2, iters=12, flow_init=None, mode="sintel"):
+        """evaluate.py's `padder = InputPadder(image1.shape, mode); flow_low, flow_pr = model(*padder.pad(image1, image2), iters, flow_init,
+        test_mode=True); flow_up = padder.unpad(flow_pr)` for frames of ANY size: -> (flow_low [N,2,Hp/8,Wp/8], flow_up [N,2,H,W]), Hp x Wp
+        the padded frame.  The padded images, their cat, the padded prediction and its slice are never formed (ops.raft_images_padded,
+        ops.upsample_flow_crop / ops.upflow8_crop).  flow_init [N,2,Hp/8,Wp/8].  The model must be in eval mode.  No gradients."""
+        who = "RAFT.predict"
+        contiguous = lambda t: t.contiguous() if isinstance(t, torch.Tensor) else t
+        image1 = check_tensor(contiguous(image1), "image1", who, (None, 3, None, None), "[N,3,H,W]")
+        N, _, H, W = image1.shape
+        image2 = check_tensor(contiguous(image2), "image2", who, (N, 3, H, W), "[N,3,H,W] like image1")
+        padder = InputPadder((H, W), mode)
+        Hp, Wp = H + padder._pad[2] + padder._pad[3], W + padder._pad[0] + padder._pad[1]
+        side = 8 * 2 ** self.args.corr_levels
+        if Hp < side or Wp < side:
+            raise MpiFlowHipError("%s: the padded frame must be at least %d x %d (got %d x %d, padded to %d x %d): at 1/8 resolution every one of "
+                                  "the %d correlation levels needs 2 x 2 cells" % (who, side, side, H, W, Hp, Wp, self.args.corr_levels))
+        tensors = dict(image1=image1, image2=image2)
+        if flow_init is not None:
+            tensors["flow_init"] = check_tensor(contiguous(flow_init), "flow_init", who, (N, 2, Hp // 8, Wp // 8), "[N,2,Hp/8,Wp/8] of the padded frame")
+        if self.training:
+            raise MpiFlowHipError("%s: the model is in training mode, where batch norm would update its running statistics during evaluation; "
+                                  "call .eval() first" % who)
+        check_devices(who, tensors)
+        pair = padder.pair(image1, image2)                      # [2N,3,Hp,Wp]
+        return self._refine(pair, iters, tensors.get("flow_init"), True, False, crop=padder._pad)

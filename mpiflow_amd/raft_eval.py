@@ -1,0 +1,84 @@
+"""RAFT evaluation (RAFT/evaluate.py) on frames of any size: upstream's InputPadder, and the numbers of validate_chairs / validate_sintel /
+validate_kitti accumulated on the device.
+
+    from mpiflow_amd.raft import RAFT
+    from mpiflow_amd.raft_eval import FlowMetrics, InputPadder
+    model = RAFT(args).cuda().eval()
+    metrics = FlowMetrics()
+    for image1, image2, flow_gt, valid_gt in dataset:                    # [3,H,W], [3,H,W], [2,H,W], [H,W]: any H, W
+        flow_low, flow_pr = model.predict(image1[None].cuda(), image2[None].cuda(), iters=24, mode="kitti")
+        metrics.update(flow_pr, flow_gt[None].cuda(), valid_gt[None].cuda())     # no host copy, no synchronisation
+    print(metrics.result("kitti"))                                       # one device-to-host copy: {'kitti-epe': ..., 'kitti-f1': ...}
+
+InputPadder is RAFT/core/utils/utils.py's class: the same constructor, `_pad = [left, right, top, bottom]`, pad() and unpad(), plus pair():
+the scaled and padded [2N,3,Hp,Wp] batch RAFT's feature network takes, in one launch (ops.raft_images_padded), which RAFT.predict uses.
+
+FlowMetrics.update launches mpf_flow_metrics (ops.flow_metrics): per frame six float64 sums stay on the device.  A pixel counts when
+valid >= 0.5 (every pixel without valid); sequence_loss's max_flow rule is NOT applied: evaluate.py has none.  result() copies them once.
+
+Not here: warm start's forward_interpolate, the dataset readers, the submission writers, mixed_precision.
+"""
+import torch
+import torch.nn.functional as F
+
+from . import ops
+from ._lib import MpiFlowHipError
+
+
+class InputPadder:
+    """Pads images such that dimensions are divisible by 8 (upstream's class).  dims: a shape whose last two entries are H, W; mode 'sintel'
+    splits both pads, any other mode (upstream passes 'kitti') puts the whole height pad at the bottom."""
+
+    def __init__(self, dims, mode="sintel"):
+        self.ht, self.wd = dims[-2:]
+        pad_ht = (((self.ht // 8) + 1) * 8 - self.ht) % 8
+        pad_wd = (((self.wd // 8) + 1) * 8 - self.wd) % 8
+        if mode == "sintel":
+            self._pad = [pad_wd // 2, pad_wd - pad_wd // 2, pad_ht // 2, pad_ht - pad_ht // 2]
+        else:
+            self._pad = [pad_wd // 2, pad_wd - pad_wd // 2, 0, pad_ht]
+
+    def pad(self, *inputs):
+        return [F.pad(x, self._pad, mode="replicate") for x in inputs]
+
+    def unpad(self, x):
+        ht, wd = x.shape[-2:]
+        c = [self._pad[2], ht - self._pad[3], self._pad[0], wd - self._pad[1]]
+        return x[..., c[0]:c[1], c[2]:c[3]]
+
+    def pair(self, image1, image2):
+        """image1, image2 [N,3,H,W] float32 in 0..255 on the GPU -> [2N,3,Hp,Wp]: 2 * (x / 255) - 1 of both padded images, image1 first, without
+        the padded images (ops.raft_images_padded).  The tensors are taken as they are or refused (MpiFlowHipError)."""
+        if isinstance(image1, torch.Tensor) and image1.dim() == 4 and tuple(image1.shape[-2:]) != (self.ht, self.wd):
+            raise MpiFlowHipError("InputPadder.pair: the padder was made for %d x %d frames (got image1 of shape %s)" % (self.ht, self.wd, tuple(image1.shape)))
+        return ops.raft_images_padded(image1, image2, self._pad)
+
+
+class FlowMetrics:
+    """The accumulators of evaluate.py's validation loops, kept on the device.  update() per batch; result(kind) once at the end."""
+
+    def __init__(self):
+        self._acc = []                                       # per update a float64 device tensor [N,6]
+
+    def update(self, flow_pr, flow_gt, valid=None):
+        """flow_pr, flow_gt [N,2,H,W], valid [N,H,W] or None, float32 on the GPU; frames of different sizes may be mixed across updates"""
+        self._acc.append(ops.flow_metrics(flow_pr, flow_gt, valid))
+
+    def result(self, kind="sintel"):
+        """kind 'sintel' (also chairs): {'epe', '1px', '3px', '5px'} over all counted pixels of all frames, np.mean(np.concatenate(epe_list)) and
+        its companions.  kind 'kitti': {'kitti-epe': the mean over frames of each frame's mean epe over its valid pixels, 'kitti-f1': 100 *
+        outliers / valid pixels over all frames} (validate_kitti).  A frame without a counted pixel has the mean nan, as upstream's empty
+        .mean().  Python floats; one device-to-host copy."""
+        if kind not in ("sintel", "kitti"):
+            raise MpiFlowHipError("FlowMetrics.result: kind must be 'sintel' or 'kitti' (got %r)" % (kind,))
+        if not self._acc:
+            raise MpiFlowHipError("FlowMetrics.result: no frame has been added (call update first)")
+        devices = {a.device for a in self._acc}
+        if len(devices) > 1:
+            raise MpiFlowHipError("FlowMetrics.result: the updates ran on %d devices; keep one FlowMetrics per device" % len(devices))
+        rows = torch.cat(self._acc, dim=0).cpu().tolist()
+        ratio = lambda num, den: num / den if den else float("nan")
+        total = [sum(r[q] for r in rows) for q in range(6)]
+        if kind == "sintel":
+            return {"epe": ratio(total[0], total[1]), "1px": ratio(total[2], total[1]), "3px": ratio(total[3], total[1]), "5px": ratio(total[4], total[1])}
+        return {"kitti-epe": sum(ratio(r[0], r[1]) for r in rows) / len(rows), "kitti-f1": 100.0 * ratio(total[5], total[1])}
