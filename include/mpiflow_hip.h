@@ -43,7 +43,8 @@ extern "C" {
                              mpf_norm_act_backward with MpfNormTerm / MpfNormArgs, and now mpf_raft_images, mpf_context_split, mpf_upflow8 and
                              their _backward calls with MpfRaftGlueArgs, and now mpf_upflow8_loss_term, its _backward call and
                              mpf_upflow8_loss_workspace with MpfUpsampleArgs, and now mpf_raft_images_padded, mpf_upsample_flow_crop, mpf_upflow8_crop,
-                             mpf_flow_metrics and mpf_flow_metrics_workspace with MpfRaftEvalArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
+                             mpf_flow_metrics and mpf_flow_metrics_workspace with MpfRaftEvalArgs, and now mpf_grad_norm, mpf_adamw_clipped and
+                             mpf_adamw_workspace with MpfOptTensor / MpfAdamWArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
 
 /* d_params layout (floats):
  *   [0..8]   K_src^-1 (3x3 row-major)            [9..20]  G_tgt_src rows 0..2 (3x4 row-major: R | t)
@@ -714,6 +715,62 @@ int mpf_upsample_flow_crop(const MpfRaftEvalArgs *a, void *stream);
 int mpf_upflow8_crop(const MpfRaftEvalArgs *a, void *stream);
 size_t mpf_flow_metrics_workspace(int N, int H, int W);   /* 0 for a shape the call refuses */
 int mpf_flow_metrics(const MpfRaftEvalArgs *a, void *stream);
+
+/* The optimizer tail of RAFT/train.py (train.py:178-181: clip_grad_norm_, AdamW.step) over a whole parameter set, as one multi-tensor path:
+ * the global gradient norm, the clip coefficient and torch's single-tensor AdamW update, without host synchronisation.  All tensors f32.
+ *   mpf_grad_norm        total_norm [1] <- (float) sqrt(sum over every record with a gradient of g * g), the sum in f64: what clip_grad_norm_
+ *                        returns.  Nothing else the caller owns is written.  The workspace keeps the sum (see norm_ready).
+ *   mpf_adamw_clipped    the same norm, then coef = min(1, max_norm / (total_norm + 1e-6f)) in f32 (a NaN norm stays NaN) and per element, with
+ *                        g = coef * grad, in f32 with every operation rounded on its own (no fused multiply-add; divide and sqrt correctly
+ *                        rounded):
+ *                            p = p * (1 - lr * weight_decay)
+ *                            m = m + (1 - beta1) * (g - m)
+ *                            v = beta2 * v + ((1 - beta2) * g) * g
+ *                            p = p - ((lr / bias_correction1) * m) / (sqrt(v) / bias_correction2_sqrt + eps)
+ *                        p, m and v are stored; grad is read only, or with zero_grad overwritten by zeros.  The five scalars in brackets and
+ *                        beta2, bias_correction2_sqrt, eps are formed in double on the host and rounded to f32 once, as torch forms them.
+ *                        coef == 1 (max_norm = +inf, or a norm below max_norm) multiplies exactly: the results are the unclipped ones bit for bit.
+ * A record whose grad is NULL is skipped as torch skips `p.grad is None`: it is not counted in the norm and nothing of it is read or written.
+ * The table `tensors` is a HOST array; the call copies at most MPF_OPT_TENSORS_PER_LAUNCH records into the arguments of each kernel launch,
+ * so nothing the caller owns has to outlive the call and the pointers may change from call to call.  One workgroup handles MPF_OPT_CHUNK
+ * consecutive elements of one tensor.  The norm: one f64 partial per workgroup, folded by one workgroup in a fixed order; no atomics, so every
+ * result is bit-identical from run to run, and the same for any alignment of the tensors.  Tensors whose four pointers are 16-byte aligned are
+ * read and written 16 bytes at a time; any 4-byte alignment works (an offset view).
+ * workspace: mpf_adamw_workspace(tensors, count) bytes, 8-byte aligned: MPF_OPT_WORKSPACE_TAIL bytes (the sum of squares f64, the norm and the
+ * coefficient f32) followed by one f64 per chunk of every record, whether its grad is NULL or not.  Contents irrelevant before the call.
+ * norm_ready = 1 (mpf_adamw_clipped; several parameter groups under one global norm): the workspace is the one an earlier mpf_grad_norm on this
+ * stream left, over whatever table that call had; this call takes the sum from it, forms total_norm and the coefficient for its own max_norm
+ * and updates its own table.  MPF_OPT_WORKSPACE_TAIL bytes suffice then.
+ * Validated before anything is launched (MPF_ERR_BAD_ARGUMENT): a NULL block, table, total_norm or workspace; count < 1; numel < 1; more than
+ * MPF_OPT_MAX_CHUNKS chunks in all; a NULL param / exp_avg / exp_avg_sq (mpf_adamw_clipped) of a record with a gradient; a pointer that is not
+ * 4-byte aligned; a workspace that is too small or not 8-byte aligned; and, by mpf_adamw_clipped, lr < 0, eps <= 0, weight_decay < 0, a beta
+ * outside [0, 1), a bias correction outside (0, 1], max_norm <= 0 or NaN, any non-finite hyperparameter other than max_norm = +inf.
+ * mpf_grad_norm reads no hyperparameter. */
+#define MPF_OPT_CHUNK 4096               /* elements one workgroup handles */
+#define MPF_OPT_TENSORS_PER_LAUNCH 64    /* tensor records passed by value per kernel launch */
+#define MPF_OPT_WORKSPACE_TAIL 16        /* bytes at the head of the workspace: f64 sum of squares, f32 norm, f32 coefficient */
+#define MPF_OPT_MAX_CHUNKS 8388608       /* 2^23: chunks of one call (a grid dimension of 256-thread workgroups stays below 2^31 threads) */
+typedef struct MpfOptTensor {
+    float *param, *exp_avg, *exp_avg_sq;     /* [numel] each, updated in place */
+    float *grad;                             /* [numel], or NULL: the record is skipped */
+    int64_t numel;
+} MpfOptTensor;
+typedef struct MpfAdamWArgs {
+    const MpfOptTensor *tensors;             /* HOST array of `count` records; device pointers inside */
+    int count;
+    int zero_grad;                           /* 1: write zeros to every grad after it is consumed */
+    int norm_ready;                          /* 1: take the sum of squares an earlier mpf_grad_norm left in the workspace */
+    double lr, beta1, beta2, eps, weight_decay;
+    double bias_correction1;                 /* 1 - beta1^t */
+    double bias_correction2_sqrt;            /* sqrt(1 - beta2^t) */
+    double max_norm;                         /* > 0; +inf = no clipping */
+    float *total_norm;                       /* device, [1], written: the norm before clipping */
+    void *workspace;
+    size_t workspace_bytes;
+} MpfAdamWArgs;
+size_t mpf_adamw_workspace(const MpfOptTensor *tensors, int count);   /* 0 for a table the calls refuse */
+int mpf_grad_norm(const MpfAdamWArgs *a, void *stream);
+int mpf_adamw_clipped(const MpfAdamWArgs *a, void *stream);
 
 /* [3,H,W] float RGB -> [H,W,3] u8 BGR, clip(rint(x*255))  (utils/utils.py:174-177) */
 int mpf_to_u8_bgr(const float *d_img, int H, int W, uint8_t *d_out, void *stream);

@@ -171,6 +171,25 @@ class MpfRaftEvalArgs(ctypes.Structure):
                 ("N", c_i), ("H", c_i), ("W", c_i), ("pad_left", c_i), ("pad_right", c_i), ("pad_top", c_i), ("pad_bottom", c_i)]
 
 
+OPT_CHUNK = 4096                # MPF_OPT_CHUNK
+OPT_TENSORS_PER_LAUNCH = 64     # MPF_OPT_TENSORS_PER_LAUNCH
+OPT_WORKSPACE_TAIL = 16         # MPF_OPT_WORKSPACE_TAIL
+OPT_MAX_CHUNKS = 1 << 23        # MPF_OPT_MAX_CHUNKS
+
+
+class MpfOptTensor(ctypes.Structure):
+    """struct MpfOptTensor of include/mpiflow_hip.h: one parameter with its AdamW moments and its gradient (device pointers; grad may be NULL)."""
+    _fields_ = [("param", c_p), ("exp_avg", c_p), ("exp_avg_sq", c_p), ("grad", c_p), ("numel", c_i64)]
+
+
+class MpfAdamWArgs(ctypes.Structure):
+    """struct MpfAdamWArgs of include/mpiflow_hip.h: the clipped AdamW step over a host table of MpfOptTensor records."""
+    _fields_ = [("tensors", ctypes.POINTER(MpfOptTensor)), ("count", c_i), ("zero_grad", c_i), ("norm_ready", c_i),
+                ("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("weight_decay", ctypes.c_double), ("bias_correction1", ctypes.c_double), ("bias_correction2_sqrt", ctypes.c_double),
+                ("max_norm", ctypes.c_double), ("total_norm", c_p), ("workspace", c_p), ("workspace_bytes", c_sz)]
+
+
 MAX_VIEWS = 16          # MPF_MAX_VIEWS
 SUPPORT_CELL_W, SUPPORT_CELL_H = 32, 8      # MPF_SUPPORT_CELL_W / _H
 
@@ -245,6 +264,9 @@ SIGNATURES = {
     "mpf_upflow8_crop": (c_i, [ctypes.POINTER(MpfRaftEvalArgs), c_p]),
     "mpf_flow_metrics_workspace": (c_sz, [c_i, c_i, c_i]),
     "mpf_flow_metrics": (c_i, [ctypes.POINTER(MpfRaftEvalArgs), c_p]),
+    "mpf_adamw_workspace": (c_sz, [ctypes.POINTER(MpfOptTensor), c_i]),
+    "mpf_grad_norm": (c_i, [ctypes.POINTER(MpfAdamWArgs), c_p]),
+    "mpf_adamw_clipped": (c_i, [ctypes.POINTER(MpfAdamWArgs), c_p]),
     "mpf_src_xyz": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
     "mpf_transform_xyz": (c_i, [c_p, c_p, c_i, c_i64, c_p, c_p]),
     "mpf_homography_sample": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),

@@ -1439,6 +1439,125 @@ def flow_metrics(flow_pr, flow_gt, valid=None):
     return acc
 
 
+def _opt_table(who, columns, names):
+    """The host table of mpf_grad_norm / mpf_adamw_clipped from parallel lists of tensors, `names` their names, the first column the one whose
+    shape the others of a record must have and the LAST the gradients, where None skips the record.  Every tensor is held to the contract of
+    _tensors.py in its order.  -> (MpfOptTensor array, device)"""
+    n = len(columns[0])
+    if n < 1 or any(len(c) != n for c in columns):
+        raise _lib.MpiFlowHipError("%s: needs %s as lists of one length, at least 1 (got %s)" % (who, ", ".join(names), ", ".join(str(len(c)) for c in columns)))
+    T = torch.Tensor
+    dev = None
+    fast = True
+    for rec in zip(*columns):
+        lead = rec[0] if rec[0] is not None else rec[-1]
+        if lead is None:
+            continue
+        if not isinstance(lead, T):
+            fast = False
+            break
+        shape = lead.shape
+        dev = lead.device if dev is None else dev
+        for t in rec:
+            if t is None and t is rec[-1]:
+                continue
+            if not (isinstance(t, T) and t.dtype == _f32 and t.shape == shape and t.is_contiguous() and t.device == dev and t.is_cuda):
+                fast = False
+                break
+        if not fast:
+            break
+    if not fast:                                                         # name the fault, in the contract's order
+        tensors = {}
+        for i, rec in enumerate(zip(*columns)):
+            lead = rec[0] if rec[0] is not None else rec[-1]
+            for name, t in zip(names, rec):
+                if t is None and name == names[-1]:
+                    continue
+                if t is lead or not isinstance(lead, T):                 # its own shape is free; a lead that is no tensor is named first
+                    shape, layout = (t.dim() if isinstance(t, T) else 0), None
+                else:
+                    shape, layout = tuple(lead.shape), "of the shape of its record's first tensor, %s" % (tuple(lead.shape),)
+                tensors["%s[%d]" % (name, i)] = check_tensor(t, "%s[%d]" % (name, i), who, shape, layout)
+        check_devices(who, tensors)
+        raise AssertionError("unreachable: the fast check and the contract disagree")
+    table = (_lib.MpfOptTensor * n)()
+    fields = ("param", "exp_avg", "exp_avg_sq", "grad") if len(columns) == 4 else ("grad",)
+    for i, rec in enumerate(zip(*columns)):
+        r = table[i]
+        lead = rec[0] if rec[0] is not None else rec[-1]
+        r.numel = lead.numel() if lead is not None else 1
+        if rec[-1] is None:
+            continue                                                     # grad stays NULL: the library skips the record
+        for f, t in zip(fields, rec):
+            setattr(r, f, t.data_ptr())
+    if dev is None:
+        raise _lib.MpiFlowHipError("%s: every entry of %s is None: there is nothing to do and no device to do it on" % (who, names[-1]))
+    return table, dev
+
+
+def _opt_args(table, dev, workspace=None):
+    """MpfAdamWArgs over `table` with total_norm [1] and the workspace (a new one, or the one an earlier grad_norm kept)"""
+    lib = _lib.load()
+    a = _lib.MpfAdamWArgs()
+    a.tensors, a.count = table, len(table)
+    total = torch.empty(1, dtype=_f32, device=dev)
+    if workspace is None:
+        need = int(lib.mpf_adamw_workspace(table, len(table)))
+        if not need:
+            raise _lib.MpiFlowHipError("mpf_adamw_workspace: %s" % lib.mpf_last_error().decode())
+        workspace = torch.empty(need // 8, dtype=torch.float64, device=dev)
+    a.total_norm, a.workspace, a.workspace_bytes = total.data_ptr(), workspace.data_ptr(), workspace.numel() * 8
+    return a, total, workspace
+
+
+@_on_device
+def grad_norm(grads, keep_workspace=False):
+    """mpf_grad_norm: what torch.nn.utils.clip_grad_norm_ returns, without touching a gradient: grads, a list of float32 tensors of any shapes on
+    one GPU (None entries are skipped, as `p.grad is None`) -> the [1] float32 device tensor sqrt(sum of g * g), summed in float64 in a fixed
+    order: bit-identical from run to run.  keep_workspace=True: -> (total_norm, workspace), the pair adamw_clipped's `norm` takes when several
+    parameter groups share one global norm.  Asynchronous on the current stream: no host copy, no synchronisation."""
+    who = "grad_norm"
+    table, dev = _opt_table(who, [list(grads)], ("grads",))
+    a, total, ws = _opt_args(table, dev)
+    _lib.check(_lib.load().mpf_grad_norm(ctypes.byref(a), _stream()), "mpf_grad_norm")
+    return (total, ws) if keep_workspace else total
+
+
+@_on_device
+def adamw_clipped(params, grads, exp_avgs, exp_avg_sqs, *, lr, betas, eps, weight_decay, step, max_norm, zero_grad=False, norm=None):
+    """mpf_adamw_clipped: clip_grad_norm_(params, max_norm) and torch.optim.AdamW's update of step number `step` (1 for the first) over parallel
+    lists of float32 tensors on one GPU, in place: params, exp_avgs, exp_avg_sqs are updated; grads are only read - NOT scaled, unlike
+    clip_grad_norm_ - or, with zero_grad, overwritten by zeros.  A None in grads skips its record entirely.  Within a record the four tensors
+    have one shape.  -> the [1] float32 device tensor total_norm, the norm before clipping.  max_norm=float('inf'): no clipping.
+    norm: the (total_norm, workspace) of an earlier grad_norm(all_grads, keep_workspace=True) on this stream: the coefficient then comes from
+    that norm (several parameter groups, one global norm) and the returned tensor is that norm again.
+    Nothing is copied or cast; bit-identical from run to run.  Asynchronous on the current stream: no host copy, no synchronisation."""
+    who = "adamw_clipped"
+    table, dev = _opt_table(who, [list(params), list(exp_avgs), list(exp_avg_sqs), list(grads)], ("params", "exp_avgs", "exp_avg_sqs", "grads"))
+    try:
+        step = operator.index(step)
+    except TypeError:
+        step = 0
+    if step < 1:
+        raise _lib.MpiFlowHipError("%s: step must be an integer, 1 for the first update (got %r)" % (who, step))
+    beta1, beta2 = (float(b) for b in betas)
+    if norm is not None:
+        if not (isinstance(norm, tuple) and len(norm) == 2 and isinstance(norm[1], torch.Tensor) and norm[1].dtype == torch.float64 and norm[1].dim() == 1
+                and norm[1].is_contiguous()):
+            raise _lib.MpiFlowHipError("%s: norm must be the (total_norm, workspace) pair of grad_norm(..., keep_workspace=True)" % who)
+        if norm[1].device != dev:
+            raise _lib.MpiFlowHipError("%s: norm was computed on %s, the tensors live on %s" % (who, norm[1].device, dev))
+    a, total, ws = _opt_args(table, dev, None if norm is None else norm[1])
+    a.norm_ready = 0 if norm is None else 1
+    a.zero_grad = 1 if zero_grad else 0
+    a.lr, a.beta1, a.beta2, a.eps, a.weight_decay, a.max_norm = float(lr), beta1, beta2, float(eps), float(weight_decay), float(max_norm)
+    a.bias_correction1 = 1.0 - beta1 ** step
+    a.bias_correction2_sqrt = (1.0 - beta2 ** step) ** 0.5
+    _lib.check(_lib.load().mpf_adamw_clipped(ctypes.byref(a), _stream()), "mpf_adamw_clipped")
+    del ws
+    return total
+
+
 @_on_device
 def to_u8_bgr(img_3HW):
     lib = _lib.load()
