@@ -44,7 +44,8 @@ extern "C" {
                              their _backward calls with MpfRaftGlueArgs, and now mpf_upflow8_loss_term, its _backward call and
                              mpf_upflow8_loss_workspace with MpfUpsampleArgs, and now mpf_raft_images_padded, mpf_upsample_flow_crop, mpf_upflow8_crop,
                              mpf_flow_metrics and mpf_flow_metrics_workspace with MpfRaftEvalArgs, and now mpf_grad_norm, mpf_adamw_clipped and
-                             mpf_adamw_workspace with MpfOptTensor / MpfAdamWArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
+                             mpf_adamw_workspace with MpfOptTensor / MpfAdamWArgs, and now mpf_forward_interpolate and
+                             mpf_forward_interpolate_workspace with MpfWarmStartArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
 
 /* d_params layout (floats):
  *   [0..8]   K_src^-1 (3x3 row-major)            [9..20]  G_tgt_src rows 0..2 (3x4 row-major: R | t)
@@ -715,6 +716,35 @@ int mpf_upsample_flow_crop(const MpfRaftEvalArgs *a, void *stream);
 int mpf_upflow8_crop(const MpfRaftEvalArgs *a, void *stream);
 size_t mpf_flow_metrics_workspace(int N, int H, int W);   /* 0 for a shape the call refuses */
 int mpf_flow_metrics(const MpfRaftEvalArgs *a, void *stream);
+
+/* RAFT's warm start: forward_interpolate (RAFT/core/utils/utils.py:26-54; evaluate.py: create_sintel_submission) without the host round trip.
+ * flow, out [N,2,h,w] f32, contiguous; samples are independent.  Per sample, with dx = flow[0], dy = flow[1]:
+ *   sources    every pixel (x0, y0) at x1 = (double)x0 + (double)dx, y1 = (double)y0 + (double)dy (numpy's int64 + float32), VALID iff
+ *              x1 > 0 && x1 < w && y1 > 0 && y1 < h: all four strict, as upstream's, so a pixel of column 0 with dx == 0 is no source; NaN
+ *              and +-inf fail the comparisons and drop out.
+ *   selection  every pixel (gx, gy) takes (dx, dy) of the valid source with the least d2 = (x1 - gx) * (x1 - gx) + (y1 - gy) * (y1 - gy),
+ *              in f64, each product rounded and then the sum (no fused multiply-add).  The two f32 values are copied, so the result is
+ *              bit-exact whenever the selection is: what scipy's griddata(method='nearest') returns wherever the nearest source is unique.
+ *   ties       equal d2 goes to the source with the lowest flat index y0 * w + x0 (scipy defines no order there; this rule is ours).
+ *   no source  a sample without a valid source gives zeros, a cold start (upstream: NaN; the one intended difference).
+ * Brute force, every target against every source: the work is (h * w)^2 per sample, so h * w <= MPF_WARM_MAX_HW (a 1080p frame's coarse
+ * grid, 135 x 240, is half of that), N <= 65535 and N * h * w <= MPF_WARM_MAX_NHW.  A minimum over (d2, index): no atomics, bit-identical
+ * from run to run.  workspace: mpf_forward_interpolate_workspace(N, h, w) bytes (12 bytes per target and source chunk, at most 32 chunks, rounded up to 8),
+ * 8-byte aligned, contents irrelevant before and after.  No f32 tensor needs any alignment.  out must not overlap flow.  Tensor VALUES are
+ * unrestricted; the only value-dependent address is the selected source's, an index below h * w by construction.  Validated before anything
+ * is launched (MPF_ERR_BAD_ARGUMENT): a NULL block, non-positive sizes, a shape above the limits, NULL pointers, out overlapping flow, a
+ * workspace that is NULL, misaligned or too small. */
+#define MPF_WARM_MAX_HW 65536            /* h * w of one sample */
+#define MPF_WARM_MAX_NHW 4194304         /* 2^22: N * h * w of one call (the workspace then stays below 1.5 GiB) */
+typedef struct MpfWarmStartArgs {
+    const float *flow;               /* [N,2,h,w] */
+    float *out;                      /* [N,2,h,w], written */
+    void *workspace;
+    size_t workspace_bytes;
+    int N, h, w;
+} MpfWarmStartArgs;
+size_t mpf_forward_interpolate_workspace(int N, int h, int w);   /* 0 for a shape the call refuses */
+int mpf_forward_interpolate(const MpfWarmStartArgs *a, void *stream);
 
 /* The optimizer tail of RAFT/train.py (train.py:178-181: clip_grad_norm_, AdamW.step) over a whole parameter set, as one multi-tensor path:
  * the global gradient norm, the clip coefficient and torch's single-tensor AdamW update, without host synchronisation.  All tensors f32.

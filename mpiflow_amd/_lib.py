@@ -171,6 +171,14 @@ class MpfRaftEvalArgs(ctypes.Structure):
                 ("N", c_i), ("H", c_i), ("W", c_i), ("pad_left", c_i), ("pad_right", c_i), ("pad_top", c_i), ("pad_bottom", c_i)]
 
 
+class MpfWarmStartArgs(ctypes.Structure):
+    """struct MpfWarmStartArgs of include/mpiflow_hip.h: RAFT's warm start, forward_interpolate as an exact nearest-source search."""
+    _fields_ = [("flow", c_p), ("out", c_p), ("workspace", c_p), ("workspace_bytes", c_sz), ("N", c_i), ("h", c_i), ("w", c_i)]
+
+
+WARM_MAX_HW = 65536             # MPF_WARM_MAX_HW
+WARM_MAX_NHW = 1 << 22          # MPF_WARM_MAX_NHW
+
 OPT_CHUNK = 4096                # MPF_OPT_CHUNK
 OPT_TENSORS_PER_LAUNCH = 64     # MPF_OPT_TENSORS_PER_LAUNCH
 OPT_WORKSPACE_TAIL = 16         # MPF_OPT_WORKSPACE_TAIL
@@ -264,6 +272,8 @@ SIGNATURES = {
     "mpf_upflow8_crop": (c_i, [ctypes.POINTER(MpfRaftEvalArgs), c_p]),
     "mpf_flow_metrics_workspace": (c_sz, [c_i, c_i, c_i]),
     "mpf_flow_metrics": (c_i, [ctypes.POINTER(MpfRaftEvalArgs), c_p]),
+    "mpf_forward_interpolate_workspace": (c_sz, [c_i, c_i, c_i]),
+    "mpf_forward_interpolate": (c_i, [ctypes.POINTER(MpfWarmStartArgs), c_p]),
     "mpf_adamw_workspace": (c_sz, [ctypes.POINTER(MpfOptTensor), c_i]),
     "mpf_grad_norm": (c_i, [ctypes.POINTER(MpfAdamWArgs), c_p]),
     "mpf_adamw_clipped": (c_i, [ctypes.POINTER(MpfAdamWArgs), c_p]),

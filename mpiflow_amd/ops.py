@@ -1439,6 +1439,38 @@ def flow_metrics(flow_pr, flow_gt, valid=None):
     return acc
 
 
+@_on_device
+def forward_interpolate(flow, out=None):
+    """mpf_forward_interpolate: RAFT's warm start (utils.forward_interpolate) per sample of flow [N,2,h,w] -> [N,2,h,w]: every pixel takes the
+    flow vector of the nearest VALID source, a pixel pushed along its own flow to x1 = x0 + dx, y1 = y0 + dy with 0 < x1 < w and 0 < y1 < h
+    (strict; NaN and inf drop out); squared distances in float64 without fused multiply-add, ties to the lowest flat index y0 * w + x0; a
+    sample without a valid source gives zeros.  The selected vectors are copied, so the result is scipy's griddata(method='nearest') bit for
+    bit wherever the nearest source is unique.  Brute force: h * w <= 65536 and N * h * w <= 2^22.  `out`: a contiguous tensor of flow's shape
+    to write; it must not overlap flow.  Bit-identical from run to run.  Asynchronous on the current stream: no host copy, no synchronisation."""
+    who = "forward_interpolate"
+    f = check_tensor(flow, "flow", who, (None, 2, None, None), "[N,2,h,w]")
+    N, _, h, w = f.shape
+    tensors = dict(flow=f)
+    if out is not None:
+        tensors["out"] = check_tensor(out, "out", who, (N, 2, h, w), "[N,2,h,w] like flow")
+    if N < 1 or h < 1 or w < 1:
+        raise _lib.MpiFlowHipError("%s: flow must have at least one sample and one pixel (got shape %s)" % (who, tuple(f.shape)))
+    if h * w > _lib.WARM_MAX_HW or N > 65535 or N * h * w > _lib.WARM_MAX_NHW:
+        raise _lib.MpiFlowHipError("%s: the search is brute force: h * w must be at most %d, N at most 65535 and N * h * w at most %d (got shape %s)"
+                                   % (who, _lib.WARM_MAX_HW, _lib.WARM_MAX_NHW, tuple(f.shape)))
+    check_devices(who, tensors)
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty_like(f)
+    ws = torch.empty(int(lib.mpf_forward_interpolate_workspace(N, h, w)) // 8, dtype=torch.float64, device=f.device)
+    a = _lib.MpfWarmStartArgs()
+    a.flow, a.out, a.N, a.h, a.w = f.data_ptr(), out.data_ptr(), N, h, w
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 8
+    _lib.check(lib.mpf_forward_interpolate(ctypes.byref(a), _stream()), "mpf_forward_interpolate")
+    del ws
+    return out
+
+
 def _opt_table(who, columns, names):
     """The host table of mpf_grad_norm / mpf_adamw_clipped from parallel lists of tensors, `names` their names, the first column the one whose
     shape the others of a record must have and the LAST the gradients, where None skips the record.  Every tensor is held to the contract of

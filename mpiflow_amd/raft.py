@@ -22,8 +22,10 @@ alone and upsamples nothing - what raft_upsample.sequence_loss(flows, None, ...)
 8 (upstream pads them first: utils.InputPadder) or are below 8 * 2^corr_levels = 128 (there the reference's sampler divides by zero at the
 coarsest level and every prediction is NaN).
 
-Beside forward: predict(image1, image2, iters=12, flow_init=None, mode='sintel') is evaluate.py's pad / forward(test_mode=True) / unpad for
-frames of any size, with the padding fused into the image scaling and the last prediction written as its unpadded window (raft_eval.py).
+Beside forward: predict(image1, image2, iters=12, flow_init=None, mode='sintel', warm_start=None) is evaluate.py's pad / forward(test_mode=True)
+/ unpad for frames of any size, with the padding fused into the image scaling and the last prediction written as its unpadded window
+(raft_eval.py); warm_start, the previous pair's flow_low, is pushed forward along itself on the device (ops.forward_interpolate) and used as
+flow_init: upstream's video recipe.
 
 Limits: the contract of _tensors.py: float32 images on the GPU, checked in its order (type, dtype, shape, what the call
 requires, the device last); non-contiguous images are made contiguous, as upstream does.  No CPU path, no eager fallback: MpiFlowHipError.
@@ -206,11 +208,13 @@ class RAFT(nn.Module):
         return flow_predictions
 
     @torch.no_grad()
-    def predict(self, image1, image2, iters=12, flow_init=None, mode="sintel"):
+    def predict(self, image1, image2, iters=12, flow_init=None, mode="sintel", warm_start=None):
         """evaluate.py's `padder = InputPadder(image1.shape, mode); flow_low, flow_pr = model(*padder.pad(image1, image2), iters, flow_init,
         test_mode=True); flow_up = padder.unpad(flow_pr)` for frames of ANY size: -> (flow_low [N,2,Hp/8,Wp/8], flow_up [N,2,H,W]), Hp x Wp
         the padded frame.  The padded images, their cat, the padded prediction and its slice are never formed (ops.raft_images_padded,
-        ops.upsample_flow_crop / ops.upflow8_crop).  flow_init [N,2,Hp/8,Wp/8].  The model must be in eval mode.  No gradients."""
+        ops.upsample_flow_crop / ops.upflow8_crop).  flow_init [N,2,Hp/8,Wp/8].  warm_start [N,2,Hp/8,Wp/8]: the previous pair's flow_low;
+        flow_init is then ops.forward_interpolate(warm_start), create_sintel_submission's warm start without its host round trip (give one
+        of the two, not both).  The model must be in eval mode.  No gradients."""
         who = "RAFT.predict"
         contiguous = lambda t: t.contiguous() if isinstance(t, torch.Tensor) else t
         image1 = check_tensor(contiguous(image1), "image1", who, (None, 3, None, None), "[N,3,H,W]")
@@ -225,9 +229,14 @@ class RAFT(nn.Module):
         tensors = dict(image1=image1, image2=image2)
         if flow_init is not None:
             tensors["flow_init"] = check_tensor(contiguous(flow_init), "flow_init", who, (N, 2, Hp // 8, Wp // 8), "[N,2,Hp/8,Wp/8] of the padded frame")
+        if warm_start is not None:
+            tensors["warm_start"] = check_tensor(contiguous(warm_start), "warm_start", who, (N, 2, Hp // 8, Wp // 8), "[N,2,Hp/8,Wp/8] of the padded frame")
+        if flow_init is not None and warm_start is not None:
+            raise MpiFlowHipError("%s: give flow_init or warm_start, not both: warm_start IS a flow_init, forward_interpolate(warm_start)" % who)
         if self.training:
             raise MpiFlowHipError("%s: the model is in training mode, where batch norm would update its running statistics during evaluation; "
                                   "call .eval() first" % who)
         check_devices(who, tensors)
         pair = padder.pair(image1, image2)                      # [2N,3,Hp,Wp]
-        return self._refine(pair, iters, tensors.get("flow_init"), True, False, crop=padder._pad)
+        flow_init = tensors.get("flow_init") if warm_start is None else ops.forward_interpolate(tensors["warm_start"])
+        return self._refine(pair, iters, flow_init, True, False, crop=padder._pad)

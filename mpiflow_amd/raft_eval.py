@@ -16,7 +16,17 @@ the scaled and padded [2N,3,Hp,Wp] batch RAFT's feature network takes, in one la
 FlowMetrics.update launches mpf_flow_metrics (ops.flow_metrics): per frame six float64 sums stay on the device.  A pixel counts when
 valid >= 0.5 (every pixel without valid); sequence_loss's max_flow rule is NOT applied: evaluate.py has none.  result() copies them once.
 
-Not here: warm start's forward_interpolate, the dataset readers, the submission writers, mixed_precision.
+forward_interpolate is RAFT/core/utils/utils.py's function, the warm start of create_sintel_submission, on the device
+(ops.forward_interpolate: an exact nearest-source search); upstream's line keeps working:
+
+    flow_low, flow_pr = model.predict(image1, image2, iters=32, flow_init=flow_prev)
+    flow_prev = forward_interpolate(flow_low[0])[None].cuda()            # already on the device: .cuda() is a no-op
+
+or, without the line: model.predict(image1, image2, iters=32, warm_start=flow_low_of_the_previous_pair), or the whole loop:
+
+    for flow_low, flow_pr in predict_sequence(model, frames, iters=32):  # frames: an iterable of [N,3,H,W] batches
+
+Not here: the dataset readers, the submission writers, mixed_precision.
 """
 import torch
 import torch.nn.functional as F
@@ -82,3 +92,25 @@ class FlowMetrics:
         if kind == "sintel":
             return {"epe": ratio(total[0], total[1]), "1px": ratio(total[2], total[1]), "3px": ratio(total[3], total[1]), "5px": ratio(total[4], total[1])}
         return {"kitti-epe": sum(ratio(r[0], r[1]) for r in rows) / len(rows), "kitti-f1": 100.0 * ratio(total[5], total[1])}
+
+
+def forward_interpolate(flow):
+    """upstream's utils.forward_interpolate: flow [2,h,w] -> [2,h,w] (also [N,2,h,w] -> [N,2,h,w], samples independent): every pixel takes the
+    flow vector of the nearest pixel pushed forward along its own flow (ops.forward_interpolate has the exact rule).  float32 on the GPU; the
+    result STAYS on the device (upstream returns a CPU tensor and calls .cuda() on it).  A flow without a valid source gives zeros, not NaN."""
+    if isinstance(flow, torch.Tensor) and flow.dim() == 3:
+        return ops.forward_interpolate(flow[None])[0]
+    return ops.forward_interpolate(flow)
+
+
+def predict_sequence(model, frames, iters=32, mode="sintel", warm_start=True):
+    """create_sintel_submission's loop over one video: `frames` an iterable of [N,3,H,W] batches; yields (flow_low, flow_up) of
+    model.predict(frames[t], frames[t+1], iters, mode=mode, warm_start=prev) per consecutive pair, prev the previous pair's flow_low (None for
+    the first pair, and always with warm_start=False).  Nothing but prev is kept; no host copy."""
+    prev = last = None
+    for frame in frames:
+        if last is not None:
+            flow_low, flow_up = model.predict(last, frame, iters=iters, mode=mode, warm_start=prev)
+            prev = flow_low if warm_start else None
+            yield flow_low, flow_up
+        last = frame
