@@ -45,7 +45,8 @@ extern "C" {
                              mpf_upflow8_loss_workspace with MpfUpsampleArgs, and now mpf_raft_images_padded, mpf_upsample_flow_crop, mpf_upflow8_crop,
                              mpf_flow_metrics and mpf_flow_metrics_workspace with MpfRaftEvalArgs, and now mpf_grad_norm, mpf_adamw_clipped and
                              mpf_adamw_workspace with MpfOptTensor / MpfAdamWArgs, and now mpf_forward_interpolate and
-                             mpf_forward_interpolate_workspace with MpfWarmStartArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
+                             mpf_forward_interpolate_workspace with MpfWarmStartArgs, and now mpf_flow_to_image, mpf_flow_to_image_workspace and
+                             mpf_flow_encode_kitti with MpfFlowVizArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
 
 /* d_params layout (floats):
  *   [0..8]   K_src^-1 (3x3 row-major)            [9..20]  G_tgt_src rows 0..2 (3x4 row-major: R | t)
@@ -745,6 +746,49 @@ typedef struct MpfWarmStartArgs {
 } MpfWarmStartArgs;
 size_t mpf_forward_interpolate_workspace(int N, int h, int w);   /* 0 for a shape the call refuses */
 int mpf_forward_interpolate(const MpfWarmStartArgs *a, void *stream);
+
+/* What upstream RAFT does with a prediction: demo.py's colour coding and the code of KITTI's 16-bit flow PNG.  flow [N,2,H,W] f32, contiguous.
+ *   mpf_flow_to_image        RAFT/core/utils/flow_viz.py's flow_to_image (make_colorwheel, flow_uv_to_colors) per image of the batch:
+ *                            out [N,H,W,3] u8.  Two launches, no host step between them: the per-image maximum rad_max of sqrt(u^2 + v^2)
+ *                            into the workspace (one slot per block, no atomics: a maximum has no order, bit-identical from run to run),
+ *                            then the colours.  Upstream's arithmetic at upstream's precisions: with clip != 0 first u, v <- min(max(., 0),
+ *                            clip_flow) (np.clip(flow, 0, clip_flow): upstream's lower bound IS 0); u, v <- u, v / (rad_max + 1e-5f);
+ *                            rad = sqrt(u^2 + v^2), a = atan2(-v, -u) / pi, fk = (a + 1) / 2 * 54, all f32; k0 = floor(fk), k1 = k0 + 1
+ *                            (55 wraps to 0), f = fk - k0, col = (1 - f) * wheel[k0] / 255 + f * wheel[k1] / 255, then rad <= 1 ?
+ *                            1 - rad * (1 - col) : 0.75 * col, and the byte floor(255 * col), all f64.  The 55-entry wheel is built on the
+ *                            host per call as make_colorwheel builds it.  Channels R, G, B; B, G, R with convert_to_bgr != 0.  An all-zero
+ *                            image is white (atan2(-0, -0) = -pi).  Against numpy the f32 atan2 may differ in its last bits, so a byte whose
+ *                            exact value lies within 0.01 of an integer may differ by 1 (tests/test_raft_flow_outputs.py).
+ *                            image [N,3,H,W] f32 in 0..255, R, G, B planes (what RAFT takes), or NULL.  With an image, out is [N,2H,W,3]: the
+ *                            frame on top, truncated toward zero as astype(uint8) and clamped to 0..255, the colours below: demo.py:viz's
+ *                            np.concatenate([img, flo], axis=0).  convert_to_bgr reverses the channels of both halves.
+ *                            NON-FINITE flow: k0 is clamped to 0..54 before it indexes the wheel, rad_max drops NaN; the colours of an image
+ *                            that holds a non-finite vector are unspecified (upstream's are, too), no address depends on them.
+ *                            workspace: mpf_flow_to_image_workspace(N, H, W) bytes, 4-byte aligned, contents irrelevant before and after.
+ *   mpf_flow_encode_kitti    frame_utils.writeFlowKITTI's array: out [N,H,W,3] u16 = (64 * u + 2^15, 64 * v + 2^15, valid), in the order the
+ *                            file holds them as R, G, B (upstream hands cv2 the reversed array as B, G, R; readFlowKITTI reverses what
+ *                            cv2 reads back).  The product and the sum are rounded in f32, as numpy's, and the code is truncated toward zero,
+ *                            as astype(uint16).  valid [N,H,W] f32 or NULL: 1 where valid >= 0.5, else 0; NULL: all ones, as upstream writes.
+ *                            THE ONE DEVIATION: a code outside 0..65535 (|flow| >= 512 px), undefined in numpy, is clamped to 0 / 65535;
+ *                            NaN gives 0.
+ * Both outputs are stored 12 bytes per lane as dwords: out must be 4-byte aligned; flow, image and valid need no alignment.  N, H, W >= 1,
+ * N <= 65535, N * H * W < 2^31 / 6.  Outputs must not overlap inputs.  Validated before anything is launched (MPF_ERR_BAD_ARGUMENT): a NULL
+ * block, non-positive or too large sizes, NULL flow or out, a misaligned out, a NaN clip_flow, a workspace that is NULL, misaligned or too small. */
+typedef struct MpfFlowVizArgs {
+    const float *flow;               /* [N,2,H,W] */
+    const float *image;              /* mpf_flow_to_image: [N,3,H,W] or NULL */
+    const float *valid;              /* mpf_flow_encode_kitti: [N,H,W] or NULL */
+    void *out;                       /* mpf_flow_to_image: u8 [N,H,W,3], [N,2H,W,3] with an image; mpf_flow_encode_kitti: u16 [N,H,W,3]; written */
+    void *workspace;                 /* mpf_flow_to_image */
+    size_t workspace_bytes;
+    int N, H, W;
+    int clip;                        /* mpf_flow_to_image: != 0: clip the flow to [0, clip_flow] first */
+    float clip_flow;
+    int convert_to_bgr;              /* mpf_flow_to_image */
+} MpfFlowVizArgs;
+size_t mpf_flow_to_image_workspace(int N, int H, int W);   /* 0 for a shape the call refuses */
+int mpf_flow_to_image(const MpfFlowVizArgs *a, void *stream);
+int mpf_flow_encode_kitti(const MpfFlowVizArgs *a, void *stream);
 
 /* The optimizer tail of RAFT/train.py (train.py:178-181: clip_grad_norm_, AdamW.step) over a whole parameter set, as one multi-tensor path:
  * the global gradient norm, the clip coefficient and torch's single-tensor AdamW update, without host synchronisation.  All tensors f32.

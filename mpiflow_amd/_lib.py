@@ -176,6 +176,12 @@ class MpfWarmStartArgs(ctypes.Structure):
     _fields_ = [("flow", c_p), ("out", c_p), ("workspace", c_p), ("workspace_bytes", c_sz), ("N", c_i), ("h", c_i), ("w", c_i)]
 
 
+class MpfFlowVizArgs(ctypes.Structure):
+    """struct MpfFlowVizArgs of include/mpiflow_hip.h: RAFT's outputs: the colour-coded flow (under the frame) and KITTI's 16-bit code."""
+    _fields_ = [("flow", c_p), ("image", c_p), ("valid", c_p), ("out", c_p), ("workspace", c_p), ("workspace_bytes", c_sz),
+                ("N", c_i), ("H", c_i), ("W", c_i), ("clip", c_i), ("clip_flow", c_f), ("convert_to_bgr", c_i)]
+
+
 WARM_MAX_HW = 65536             # MPF_WARM_MAX_HW
 WARM_MAX_NHW = 1 << 22          # MPF_WARM_MAX_NHW
 
@@ -274,6 +280,9 @@ SIGNATURES = {
     "mpf_flow_metrics": (c_i, [ctypes.POINTER(MpfRaftEvalArgs), c_p]),
     "mpf_forward_interpolate_workspace": (c_sz, [c_i, c_i, c_i]),
     "mpf_forward_interpolate": (c_i, [ctypes.POINTER(MpfWarmStartArgs), c_p]),
+    "mpf_flow_to_image_workspace": (c_sz, [c_i, c_i, c_i]),
+    "mpf_flow_to_image": (c_i, [ctypes.POINTER(MpfFlowVizArgs), c_p]),
+    "mpf_flow_encode_kitti": (c_i, [ctypes.POINTER(MpfFlowVizArgs), c_p]),
     "mpf_adamw_workspace": (c_sz, [ctypes.POINTER(MpfOptTensor), c_i]),
     "mpf_grad_norm": (c_i, [ctypes.POINTER(MpfAdamWArgs), c_p]),
     "mpf_adamw_clipped": (c_i, [ctypes.POINTER(MpfAdamWArgs), c_p]),

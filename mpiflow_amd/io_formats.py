@@ -55,6 +55,82 @@ def png_from_scanlines(scanlines_H_1p3W_u8, level=1):
     return _PNG_SIG + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) + _png_chunk(b"IDAT", idat) + _png_chunk(b"IEND", b"")
 
 
+def png16_from_rgb(img_HW3_rgb_u16, level=1):
+    """[H,W,3] uint16 in file order R, G, B -> PNG bytes: colour type 2, bit depth 16, samples big-endian (most significant byte first), filter
+    "Up" on the bytes of every row, one IDAT.  The 16-bit sibling of png_from_scanlines (KITTI's flow files, raft_eval.write_flow_kitti)."""
+    import struct
+    import zlib
+    img = np.ascontiguousarray(img_HW3_rgb_u16)
+    assert img.ndim == 3 and img.shape[2] == 3 and img.dtype == np.uint16, "png16_from_rgb takes a uint16 array [H,W,3]"
+    h, w, _ = img.shape
+    flat = img.astype(">u2").view(np.uint8).reshape(h, 6 * w)
+    sc = np.empty((h, 6 * w + 1), np.uint8)
+    sc[:, 0] = 2
+    sc[0, 1:] = flat[0]
+    np.subtract(flat[1:], flat[:-1], out=sc[1:, 1:])
+    co = zlib.compressobj(level, zlib.DEFLATED, 15, 9, zlib.Z_RLE)
+    idat = co.compress(sc.data) + co.flush()
+    return _PNG_SIG + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 16, 2, 0, 0, 0)) + _png_chunk(b"IDAT", idat) + _png_chunk(b"IEND", b"")
+
+
+def read_png_rgb(data_or_path):
+    """The inverse of png_from_scanlines / png16_from_rgb, and of any other writer's non-interlaced truecolour PNG: bytes or a path ->
+    [H,W,3] uint8 (bit depth 8) or uint16 (bit depth 16) in file order R, G, B.  All five row filters.  No OpenCV, no Pillow."""
+    import struct
+    import zlib
+    data = data_or_path
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        with open(data_or_path, "rb") as f:
+            data = f.read()
+    data = bytes(data)
+    if data[:8] != _PNG_SIG:
+        raise ValueError("not a PNG file")
+    pos, idat, head = 8, [], None
+    while pos + 8 <= len(data):
+        n, tag = struct.unpack(">I4s", data[pos:pos + 8])
+        body = data[pos + 8:pos + 8 + n]
+        if tag == b"IHDR":
+            head = struct.unpack(">IIBBBBB", body)
+        elif tag == b"IDAT":
+            idat.append(body)
+        elif tag == b"IEND":
+            break
+        pos += 12 + n
+    if head is None or head[3] != 2 or head[2] not in (8, 16) or head[6] != 0:
+        raise ValueError("read_png_rgb reads non-interlaced truecolour PNGs of bit depth 8 or 16 (IHDR: %s)" % (head,))
+    w, h, depth = head[0], head[1], head[2]
+    bpp, row = 3 * depth // 8, 3 * depth // 8 * w
+    raw = np.frombuffer(zlib.decompress(b"".join(idat)), np.uint8)
+    if raw.size != h * (row + 1):
+        raise ValueError("PNG data holds %d bytes, %d expected" % (raw.size, h * (row + 1)))
+    raw = raw.reshape(h, row + 1)
+    out = np.zeros((h + 1, bpp + row), np.uint8)               # a zero row above and bpp zero bytes to the left: the filters' missing neighbours
+    for y in range(h):
+        ft, line, cur, up = int(raw[y, 0]), raw[y, 1:], out[y + 1], out[y]
+        if ft == 0:
+            cur[bpp:] = line
+        elif ft == 2:
+            cur[bpp:] = line + up[bpp:]
+        elif ft in (1, 3, 4):
+            ln, upl, c = line.tolist(), up.tolist(), [0] * (bpp + row)
+            for i in range(row):
+                a, b, d = c[i], upl[i + bpp], upl[i]
+                if ft == 1:
+                    pred = a
+                elif ft == 3:
+                    pred = (a + b) >> 1
+                else:
+                    p = a + b - d
+                    pa, pb, pd = abs(p - a), abs(p - b), abs(p - d)
+                    pred = a if pa <= pb and pa <= pd else (b if pb <= pd else d)
+                c[i + bpp] = (ln[i] + pred) & 255
+            cur[:] = c
+        else:
+            raise ValueError("PNG row %d has the unknown filter type %d" % (y, ft))
+    px = np.ascontiguousarray(out[1:, bpp:])
+    return px.reshape(h, w, 3) if depth == 8 else px.view(">u2").astype(np.uint16).reshape(h, w, 3)
+
+
 def filter_up_rgb(img_HW3_rgb_u8):
     """Host version of mpf_png_filter_up for RGB input: [H,W,3] u8 -> scanlines [H, 1+3W]"""
     img = np.ascontiguousarray(img_HW3_rgb_u8, dtype=np.uint8)

@@ -1471,6 +1471,93 @@ def forward_interpolate(flow, out=None):
     return out
 
 
+def _check_out_int(t, who, dtype, shape, layout):
+    """check_tensor's rule for an integer `out` (the float32 test replaced by `dtype`): type, dtype, shape, contiguity; the 4-byte alignment
+    the kernels' dword stores need.  Returns t itself."""
+    if not isinstance(t, torch.Tensor):
+        raise _lib.MpiFlowHipError("%s: out must be a torch.Tensor (got %s)" % (who, type(t).__name__))
+    if t.dtype != dtype:
+        raise _lib.MpiFlowHipError("%s: out must be %s (got %s)" % (who, str(dtype).replace("torch.", ""), t.dtype))
+    if tuple(t.shape) != tuple(shape):
+        raise _lib.MpiFlowHipError("%s: out must be %s, a contiguous tensor of %d dimensions (got shape %s)" % (who, layout, len(shape), tuple(t.shape)))
+    if not t.is_contiguous():
+        raise _lib.MpiFlowHipError("%s: out must be contiguous (got shape %s with strides %s)" % (who, tuple(t.shape), t.stride()))
+    if t.data_ptr() % 4:
+        raise _lib.MpiFlowHipError("%s: out must be 4-byte aligned (it is stored a dword at a time; got a view at offset %d)" % (who, t.storage_offset()))
+    return t
+
+
+@_on_device
+def flow_to_image(flow, image=None, clip_flow=None, convert_to_bgr=False, out=None):
+    """mpf_flow_to_image: RAFT/core/utils/flow_viz.py's flow_to_image per image of a batch, on the device: flow [N,2,H,W] -> uint8 [N,H,W,3], the
+    colour wheel at upstream's precisions (float32 u, v, rad, atan2, fk; float64 wheel, blend and floor), normalised by each image's own
+    rad_max + 1e-5.  clip_flow: upstream's np.clip(flow, 0, clip_flow) first (its lower bound is 0).  convert_to_bgr: channels B, G, R.
+    image [N,3,H,W] in 0..255 (what RAFT.predict takes): the result is [N,2H,W,3], the frame truncated to uint8 on top and the colours below
+    (demo.py:viz); convert_to_bgr reverses both halves, which is the layout ops.png_scanlines takes.  Against numpy a byte whose exact value
+    lies within 0.01 of an integer may differ by 1 (the float32 atan2's last bits); every other byte is equal.  The colours of an image that
+    holds a NaN or inf vector are unspecified.  `out`: a contiguous uint8 tensor of the result's shape to write.  float32, contiguous, on the
+    GPU, or MpiFlowHipError.  Two launches, bit-identical from run to run, asynchronous on the current stream: no host copy, no
+    synchronisation."""
+    who = "flow_to_image"
+    f = check_tensor(flow, "flow", who, (None, 2, None, None), "[N,2,H,W]")
+    N, _, H, W = f.shape
+    tensors = dict(flow=f)
+    if image is not None:
+        tensors["image"] = check_tensor(image, "image", who, (N, 3, H, W), "[N,3,H,W] like flow")
+    rows = 2 * H if image is not None else H
+    if out is not None:
+        tensors["out"] = _check_out_int(out, who, torch.uint8, (N, rows, W, 3), "[N,2H,W,3]" if image is not None else "[N,H,W,3]")
+    if N < 1 or H < 1 or W < 1:
+        raise _lib.MpiFlowHipError("%s: flow must have at least one image and one pixel (got shape %s)" % (who, tuple(f.shape)))
+    if clip_flow is not None:
+        try:
+            clip = float(clip_flow)
+        except (TypeError, ValueError):
+            clip = float("nan")
+        if clip != clip:
+            raise _lib.MpiFlowHipError("%s: clip_flow must be None or a number (got %r)" % (who, clip_flow))
+        clip_flow = clip
+    check_devices(who, tensors)
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty((N, rows, W, 3), dtype=torch.uint8, device=f.device)
+    ws = torch.empty(int(lib.mpf_flow_to_image_workspace(N, H, W)) // 4, dtype=_f32, device=f.device)
+    a = _lib.MpfFlowVizArgs()
+    a.flow, a.image, a.out, a.N, a.H, a.W = f.data_ptr(), (image.data_ptr() if image is not None else None), out.data_ptr(), N, H, W
+    a.clip, a.clip_flow, a.convert_to_bgr = int(clip_flow is not None), (clip_flow or 0.0), int(bool(convert_to_bgr))
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    _lib.check(lib.mpf_flow_to_image(ctypes.byref(a), _stream()), "mpf_flow_to_image")
+    del ws
+    return out
+
+
+@_on_device
+def flow_encode_kitti(flow, valid=None, out=None):
+    """mpf_flow_encode_kitti: the array frame_utils.writeFlowKITTI hands to the PNG encoder, on the device: flow [N,2,H,W], valid [N,H,W] or None
+    -> uint16 [N,H,W,3] = (64 * u + 2^15, 64 * v + 2^15, valid), the order the file holds as R, G, B (upstream passes cv2 the reverse, as B, G,
+    R, and readFlowKITTI reverses what cv2 reads back).  Product and sum in float32, truncated toward zero, as upstream's astype(np.uint16).
+    valid: 1 where valid >= 0.5, else 0; None: all ones, as upstream writes.  The one deviation: a code outside 0..65535 (|flow| >= 512 px),
+    undefined in numpy, is clamped to 0 / 65535 (NaN: 0).  `out`: a contiguous uint16 tensor [N,H,W,3] to write.  float32, contiguous, on the
+    GPU, or MpiFlowHipError.  One launch, asynchronous on the current stream."""
+    who = "flow_encode_kitti"
+    f = check_tensor(flow, "flow", who, (None, 2, None, None), "[N,2,H,W]")
+    N, _, H, W = f.shape
+    tensors = dict(flow=f)
+    if valid is not None:
+        tensors["valid"] = check_tensor(valid, "valid", who, (N, H, W), "[N,H,W] like flow")
+    if out is not None:
+        tensors["out"] = _check_out_int(out, who, torch.uint16, (N, H, W, 3), "[N,H,W,3]")
+    if N < 1 or H < 1 or W < 1:
+        raise _lib.MpiFlowHipError("%s: flow must have at least one image and one pixel (got shape %s)" % (who, tuple(f.shape)))
+    check_devices(who, tensors)
+    if out is None:
+        out = torch.empty((N, H, W, 3), dtype=torch.uint16, device=f.device)
+    a = _lib.MpfFlowVizArgs()
+    a.flow, a.valid, a.out, a.N, a.H, a.W = f.data_ptr(), (valid.data_ptr() if valid is not None else None), out.data_ptr(), N, H, W
+    _lib.check(_lib.load().mpf_flow_encode_kitti(ctypes.byref(a), _stream()), "mpf_flow_encode_kitti")
+    return out
+
+
 def _opt_table(who, columns, names):
     """The host table of mpf_grad_norm / mpf_adamw_clipped from parallel lists of tensors, `names` their names, the first column the one whose
     shape the others of a record must have and the LAST the gradients, where None skips the record.  Every tensor is held to the contract of

@@ -26,12 +26,18 @@ or, without the line: model.predict(image1, image2, iters=32, warm_start=flow_lo
 
     for flow_low, flow_pr in predict_sequence(model, frames, iters=32):  # frames: an iterable of [N,3,H,W] batches
 
-Not here: the dataset readers, the submission writers, mixed_precision.
+What upstream does with a prediction: flow_to_image is flow_viz.flow_to_image on the device, save_flow_image
+demo.py's picture as a PNG, write_flow_kitti / read_flow_kitti frame_utils' KITTI pair without OpenCV; .flo is io_formats.write_flo.
+
+    picture = flow_to_image(flow_pr, image=image1)                       # uint8 [N,2H,W,3] on the device: the frame above its colour-coded flow
+    write_flow_kitti("000000_10.png", flow_pr[0])                        # create_kitti_submission's file
+
+Not here: the dataset readers, mixed_precision.
 """
 import torch
 import torch.nn.functional as F
 
-from . import ops
+from . import io_formats, ops
 from ._lib import MpiFlowHipError
 
 
@@ -101,6 +107,54 @@ def forward_interpolate(flow):
     if isinstance(flow, torch.Tensor) and flow.dim() == 3:
         return ops.forward_interpolate(flow[None])[0]
     return ops.forward_interpolate(flow)
+
+
+def flow_to_image(flow, image=None, clip_flow=None, convert_to_bgr=False):
+    """upstream's flow_viz.flow_to_image on the device (ops.flow_to_image has the arithmetic): flow [N,2,H,W] (what RAFT.predict returns) ->
+    uint8 [N,H,W,3], every image normalised by its own largest vector, as upstream, which is called per image; or upstream's own layout, one
+    [H,W,2] tensor -> [H,W,3] (re-laid as [1,2,H,W] by a device copy).  image [N,3,H,W] ([3,H,W] beside an [H,W,2] flow) in 0..255: demo.py's
+    stack, uint8 [N,2H,W,3] with the frame on top.  float32 on the GPU; the result stays there."""
+    if isinstance(flow, torch.Tensor) and flow.dim() == 3:
+        if flow.shape[2] != 2:
+            raise MpiFlowHipError("flow_to_image: flow must be [N,2,H,W] or [H,W,2] (got shape %s)" % (tuple(flow.shape),))
+        if isinstance(image, torch.Tensor) and image.dim() == 3:
+            image = image[None]
+        return ops.flow_to_image(flow.permute(2, 0, 1).contiguous()[None], image, clip_flow, convert_to_bgr)[0]
+    return ops.flow_to_image(flow, image, clip_flow, convert_to_bgr)
+
+
+def _single(t, name, who, rank):
+    """one sample of a batch argument, for the writers of one file: [1, ...] or its unbatched form -> the batched form"""
+    if isinstance(t, torch.Tensor) and t.dim() == rank - 1:
+        return t[None]
+    if isinstance(t, torch.Tensor) and t.dim() == rank and t.shape[0] != 1:
+        raise MpiFlowHipError("%s: one file holds one image: %s must be a single sample (got shape %s)" % (who, name, tuple(t.shape)))
+    return t
+
+
+def save_flow_image(path, flow, image=None):
+    """demo.py's picture as an 8-bit PNG: the colour-coded flow [2,H,W] (or [1,2,H,W]), under the frame [3,H,W] if one is given.  Colours and
+    PNG row filter on the device (ops.flow_to_image, ops.png_scanlines); the host deflates 3 bytes per pixel.  Synchronises: it writes a file."""
+    who = "save_flow_image"
+    bgr = ops.flow_to_image(_single(flow, "flow", who, 4), None if image is None else _single(image, "image", who, 4), convert_to_bgr=True)
+    io_formats.write_bytes(path, io_formats.png_from_scanlines(ops.png_scanlines(bgr[0]).cpu().numpy()))
+
+
+def write_flow_kitti(path, flow, valid=None):
+    """frame_utils.writeFlowKITTI without OpenCV: flow [2,H,W] (or [1,2,H,W]), valid [H,W] or None (all ones, as upstream) -> KITTI's 16-bit RGB
+    PNG, R = 64 * u + 2^15, G = 64 * v + 2^15, B = valid, encoded on the device (ops.flow_encode_kitti: |flow| >= 512 px clamps).  Synchronises."""
+    who = "write_flow_kitti"
+    code = ops.flow_encode_kitti(_single(flow, "flow", who, 4), None if valid is None else _single(valid, "valid", who, 3))
+    io_formats.write_bytes(path, io_formats.png16_from_rgb(code[0].cpu().numpy()))
+
+
+def read_flow_kitti(path):
+    """frame_utils.readFlowKITTI without OpenCV: -> (flow [H,W,2] float32 = (code - 2^15) / 64, valid [H,W] float32), numpy arrays on the host"""
+    code = io_formats.read_png_rgb(path)
+    if code.dtype != "uint16":
+        raise MpiFlowHipError("read_flow_kitti: %s is no 16-bit PNG" % (path,))
+    code = code.astype("float32")
+    return (code[:, :, :2] - 2 ** 15) / 64.0, code[:, :, 2]
 
 
 def predict_sequence(model, frames, iters=32, mode="sintel", warm_start=True):
