@@ -46,7 +46,8 @@ extern "C" {
                              mpf_flow_metrics and mpf_flow_metrics_workspace with MpfRaftEvalArgs, and now mpf_grad_norm, mpf_adamw_clipped and
                              mpf_adamw_workspace with MpfOptTensor / MpfAdamWArgs, and now mpf_forward_interpolate and
                              mpf_forward_interpolate_workspace with MpfWarmStartArgs, and now mpf_flow_to_image, mpf_flow_to_image_workspace and
-                             mpf_flow_encode_kitti with MpfFlowVizArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
+                             mpf_flow_encode_kitti with MpfFlowVizArgs, and now mpf_rgbd_mesh_vertices, mpf_rasterize_grid and
+                             mpf_rasterize_grid_workspace with MpfMeshVertexArgs / MpfMeshRasterArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
 
 /* d_params layout (floats):
  *   [0..8]   K_src^-1 (3x3 row-major)            [9..20]  G_tgt_src rows 0..2 (3x4 row-major: R | t)
@@ -789,6 +790,61 @@ typedef struct MpfFlowVizArgs {
 size_t mpf_flow_to_image_workspace(int N, int H, int W);   /* 0 for a shape the call refuses */
 int mpf_flow_to_image(const MpfFlowVizArgs *a, void *stream);
 int mpf_flow_encode_kitti(const MpfFlowVizArgs *a, void *stream);
+
+/* The warp-back RGB-D mesh renderer (warpback/utils.py: RGBDRenderer) without pytorch3d.  All tensors f32 and contiguous unless stated.
+ *   mpf_rgbd_mesh_vertices   construct_mesh and the first half of render_mesh (warpback/utils.py:31-51, 84-111, 174-218) per pixel (y, x),
+ *                            vertex y * w + x, with nothing intermediate stored:
+ *                              (u, v) = ((x + 0.5) / w, (y + 0.5) / h); depth = 1 / (disp + 1e-4); P = (cam_int^-1 (u, v, 1)) * depth, each row
+ *                              (k0 u + k1 v) + k2, the inverse by the adjugate in f64 and rounded to f32 once; Wd = cam_ext (P, 1), each row
+ *                              ((e0 X + e1 Y) + e2 Z) + e3; n = (2 fx Wd.x + (2 cx - 1) Wd.z, 2 fy Wd.y + (2 cy - 1) Wd.z, a Wd.z + b),
+ *                              a = (near + far) / (far - near), b = -2 near far / (far - near) in f32 with near = 1e-4, far = 1e4;
+ *                              verts_ndc = (-(n.x / Wd.z) * float(w / h), -(n.y / Wd.z), n.z / Wd.z).
+ *                              attrs = (r, g, b, vis, Wd.z); vis = exp(-10 sqrt(gx^2 + gy^2)) > 0.3 ? 1 : 0 with gx, gy the 3 x 3 Sobel
+ *                              responses of the disparity under zero padding (get_visible_mask).
+ *                            The reference's f32 matmul and inverse associate differently: tests/test_warpback.py bounds the difference.
+ *   mpf_rasterize_grid       pytorch3d's rasterize_meshes (faces_per_pixel = 1, perspective_correct = False, clip_barycentric_coords =
+ *                            False, cull_backfaces = False, no z clipping) followed by interpolate_face_attributes, on the regular grid
+ *                            mesh of h x w vertices whose faces are implicit: Q = (h - 1)(w - 1), F = 2 Q; cell q = r (w - 1) + c has
+ *                            tl = r w + c, tr = tl + 1, bl = tl + w, br = bl + 1; face q = (tl, bl, br), face Q + q = (br, tr, tl).
+ *                            INTEGRATION.md section 16 is the definition, operation by operation (tests/warpback_restated.py restates it).
+ *                            Outputs, with the value of a pixel no face covers: pix_to_face i64 [B,h,w] = b F + f (-1); zbuf [B,h,w] (-1);
+ *                            bary [B,h,w,3], unclipped (-1); out [B,C,h,w] (+0).  The winner of a pixel is the covering face of the least
+ *                            depth, the lowest face index on equal depth; a face with a non-finite coordinate is skipped.  A 64-bit atomic
+ *                            minimum per covered pixel: identical bytes on every run.
+ *                            workspace: mpf_rasterize_grid_workspace(B, h, w) bytes (8 per pixel), 8-byte aligned, contents irrelevant
+ *                            before and after.  pix_to_face must be 8-byte aligned; no f32 tensor needs any alignment.
+ * Limits: h, w >= 2; B <= 65535; B * h * w <= MPF_MESH_MAX_BHW (so 2 (h - 1)(w - 1) < 2^31); 1 <= C <= MPF_MESH_MAX_ATTRS.  Tensor VALUES
+ * are unrestricted: no address depends on one.  No gradients.  Validated before anything is launched (MPF_ERR_BAD_ARGUMENT): a NULL block,
+ * a shape outside the limits, NULL pointers, outputs that overlap inputs, a workspace that is NULL, misaligned or too small. */
+#define MPF_MESH_MAX_ATTRS 8
+#define MPF_MESH_PASS_ALL 0              /* clear, z pass, resolve pass */
+#define MPF_MESH_PASS_Z 1                /* clear and z pass only: the keys stay in the workspace, no output is written (the four output pointers may be NULL) */
+#define MPF_MESH_PASS_RESOLVE 2          /* resolve pass only, from the keys an MPF_MESH_PASS_Z call with the same arguments left in the workspace */
+#define MPF_MESH_MAX_BHW 268435456       /* 2^28: B * h * w of one call (the workspace is then 2 GiB) */
+typedef struct MpfMeshVertexArgs {
+    const float *rgbd;               /* [B,4,h,w]: r, g, b, disparity */
+    const float *cam_int;            /* [B,3,3] */
+    const float *cam_ext;            /* [B,3,4] */
+    float *verts_ndc;                /* [B,h*w,3], written */
+    float *attrs;                    /* [B,h*w,5], written */
+    int B, h, w;
+} MpfMeshVertexArgs;
+typedef struct MpfMeshRasterArgs {
+    const float *verts_ndc;          /* [B,h*w,3] */
+    const float *attrs;              /* [B,h*w,C] */
+    int64_t *pix_to_face;            /* [B,h,w], written */
+    float *zbuf;                     /* [B,h,w], written */
+    float *bary;                     /* [B,h,w,3], written */
+    float *out;                      /* [B,C,h,w], written */
+    void *workspace;
+    size_t workspace_bytes;
+    int B, h, w, C;
+    float blur_radius;               /* a SQUARED distance in NDC units, as pytorch3d's */
+    int passes;                      /* MPF_MESH_PASS_ALL, or one half of the call on its own (tools/bench_warpback.py times them) */
+} MpfMeshRasterArgs;
+int mpf_rgbd_mesh_vertices(const MpfMeshVertexArgs *a, void *stream);
+size_t mpf_rasterize_grid_workspace(int B, int h, int w);   /* 0 for a shape the call refuses */
+int mpf_rasterize_grid(const MpfMeshRasterArgs *a, void *stream);
 
 /* The optimizer tail of RAFT/train.py (train.py:178-181: clip_grad_norm_, AdamW.step) over a whole parameter set, as one multi-tensor path:
  * the global gradient norm, the clip coefficient and torch's single-tensor AdamW update, without host synchronisation.  All tensors f32.

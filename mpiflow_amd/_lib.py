@@ -182,6 +182,21 @@ class MpfFlowVizArgs(ctypes.Structure):
                 ("N", c_i), ("H", c_i), ("W", c_i), ("clip", c_i), ("clip_flow", c_f), ("convert_to_bgr", c_i)]
 
 
+class MpfMeshVertexArgs(ctypes.Structure):
+    """struct MpfMeshVertexArgs of include/mpiflow_hip.h: the warp-back renderer's vertex stage (RGB-D -> NDC vertices and attributes)."""
+    _fields_ = [("rgbd", c_p), ("cam_int", c_p), ("cam_ext", c_p), ("verts_ndc", c_p), ("attrs", c_p), ("B", c_i), ("h", c_i), ("w", c_i)]
+
+
+class MpfMeshRasterArgs(ctypes.Structure):
+    """struct MpfMeshRasterArgs of include/mpiflow_hip.h: the warp-back renderer's rasteriser of a regular grid mesh with implicit faces."""
+    _fields_ = [("verts_ndc", c_p), ("attrs", c_p), ("pix_to_face", c_p), ("zbuf", c_p), ("bary", c_p), ("out", c_p), ("workspace", c_p),
+                ("workspace_bytes", c_sz), ("B", c_i), ("h", c_i), ("w", c_i), ("C", c_i), ("blur_radius", c_f), ("passes", c_i)]
+
+
+MESH_MAX_ATTRS = 8              # MPF_MESH_MAX_ATTRS
+MESH_PASS_ALL, MESH_PASS_Z, MESH_PASS_RESOLVE = 0, 1, 2    # MPF_MESH_PASS_*
+MESH_MAX_BHW = 1 << 28          # MPF_MESH_MAX_BHW
+
 WARM_MAX_HW = 65536             # MPF_WARM_MAX_HW
 WARM_MAX_NHW = 1 << 22          # MPF_WARM_MAX_NHW
 
@@ -283,6 +298,9 @@ SIGNATURES = {
     "mpf_flow_to_image_workspace": (c_sz, [c_i, c_i, c_i]),
     "mpf_flow_to_image": (c_i, [ctypes.POINTER(MpfFlowVizArgs), c_p]),
     "mpf_flow_encode_kitti": (c_i, [ctypes.POINTER(MpfFlowVizArgs), c_p]),
+    "mpf_rgbd_mesh_vertices": (c_i, [ctypes.POINTER(MpfMeshVertexArgs), c_p]),
+    "mpf_rasterize_grid_workspace": (c_sz, [c_i, c_i, c_i]),
+    "mpf_rasterize_grid": (c_i, [ctypes.POINTER(MpfMeshRasterArgs), c_p]),
     "mpf_adamw_workspace": (c_sz, [ctypes.POINTER(MpfOptTensor), c_i]),
     "mpf_grad_norm": (c_i, [ctypes.POINTER(MpfAdamWArgs), c_p]),
     "mpf_adamw_clipped": (c_i, [ctypes.POINTER(MpfAdamWArgs), c_p]),

@@ -1471,6 +1471,80 @@ def forward_interpolate(flow, out=None):
     return out
 
 
+def _mesh_limits(who, B, h, w):
+    if B < 1 or h < 2 or w < 2:
+        raise _lib.MpiFlowHipError("%s: a grid mesh needs at least one sample and h, w >= 2 (got B, h, w = %d, %d, %d)" % (who, B, h, w))
+    if B > 65535 or B * h * w > _lib.MESH_MAX_BHW:
+        raise _lib.MpiFlowHipError("%s: B must be at most 65535 and B * h * w at most %d (got B, h, w = %d, %d, %d)" % (who, _lib.MESH_MAX_BHW, B, h, w))
+
+
+@_on_device
+def rgbd_mesh_vertices(rgbd, cam_int, cam_ext):
+    """mpf_rgbd_mesh_vertices: RGBDRenderer.construct_mesh and the first half of render_mesh (warpback/utils.py) in one launch: rgbd [B,4,h,w]
+    (r, g, b, disparity), cam_int [B,3,3], cam_ext [B,3,4] -> (verts_ndc [B,h*w,3], attrs [B,h*w,5]).  verts_ndc: unprojected with depth =
+    1 / (disp + 1e-4), moved by the extrinsic, through the near / far perspective matrix, divided, x and y negated, x scaled by w / h.  attrs:
+    r, g, b, the Sobel visibility bit exp(-10 |grad disp|) > 0.3, the depth after the extrinsic.  cam_int is inverted in float64 by the
+    adjugate.  float32, contiguous, on the GPU, or MpiFlowHipError.  Asynchronous on the current stream: no host copy, no synchronisation."""
+    who = "rgbd_mesh_vertices"
+    x = check_tensor(rgbd, "rgbd", who, (None, 4, None, None), "[B,4,h,w]")
+    B, _, h, w = x.shape
+    K = check_tensor(cam_int, "cam_int", who, (B, 3, 3), "[B,3,3]")
+    E = check_tensor(cam_ext, "cam_ext", who, (B, 3, 4), "[B,3,4]")
+    _mesh_limits(who, B, h, w)
+    check_devices(who, dict(rgbd=x, cam_int=K, cam_ext=E))
+    verts = torch.empty((B, h * w, 3), dtype=_f32, device=x.device)
+    attrs = torch.empty((B, h * w, 5), dtype=_f32, device=x.device)
+    a = _lib.MpfMeshVertexArgs()
+    a.rgbd, a.cam_int, a.cam_ext, a.verts_ndc, a.attrs, a.B, a.h, a.w = x.data_ptr(), K.data_ptr(), E.data_ptr(), verts.data_ptr(), attrs.data_ptr(), B, h, w
+    _lib.check(_lib.load().mpf_rgbd_mesh_vertices(ctypes.byref(a), _stream()), "mpf_rgbd_mesh_vertices")
+    return verts, attrs
+
+
+@_on_device
+def rasterize_grid(verts_ndc, attrs, h, w, blur_radius=1e-6):
+    """mpf_rasterize_grid: pytorch3d's rasterize_meshes(faces_per_pixel=1, blur_radius) and interpolate_face_attributes on the regular grid mesh
+    of h x w vertices (RGBDRenderer.get_faces' faces, implicit): verts_ndc [B,h*w,3], attrs [B,h*w,C], C <= 8 -> (pix_to_face int64 [B,h,w],
+    packed b * F + f; zbuf [B,h,w]; bary [B,h,w,3], unclipped; out [B,C,h,w]).  A pixel no face covers holds -1, -1, -1 and +0.  The winner of
+    a pixel is the covering face of the least depth, the lowest face index on equal depth; a face with a non-finite coordinate is skipped;
+    blur_radius is a SQUARED distance in NDC units.  INTEGRATION.md section 16 has the definition operation by operation.  No gradients.
+    float32, contiguous, on the GPU, or MpiFlowHipError.  Identical bytes on every run.  Asynchronous on the current stream."""
+    who = "rasterize_grid"
+    v = check_tensor(verts_ndc, "verts_ndc", who, (None, None, 3), "[B,h*w,3]")
+    B, n, _ = v.shape
+    at = check_tensor(attrs, "attrs", who, (B, n, None), "[B,h*w,C] like verts_ndc")
+    C = at.shape[2]
+    try:
+        h, w = operator.index(h), operator.index(w)
+    except TypeError:
+        raise _lib.MpiFlowHipError("%s: h and w must be integers (got %r, %r)" % (who, h, w)) from None
+    if h < 2 or w < 2 or h * w != n:
+        raise _lib.MpiFlowHipError("%s: h, w must be at least 2 with h * w = %d, the vertices of verts_ndc (got h, w = %d, %d)" % (who, n, h, w))
+    if not 1 <= C <= _lib.MESH_MAX_ATTRS:
+        raise _lib.MpiFlowHipError("%s: attrs must have 1..%d channels (got %d)" % (who, _lib.MESH_MAX_ATTRS, C))
+    try:
+        blur = float(blur_radius)
+    except (TypeError, ValueError):
+        blur = float("nan")
+    if not 0.0 <= blur < float("inf"):
+        raise _lib.MpiFlowHipError("%s: blur_radius must be a finite number >= 0 (got %r)" % (who, blur_radius))
+    _mesh_limits(who, B, h, w)
+    check_devices(who, dict(verts_ndc=v, attrs=at))
+    lib = _lib.load()
+    dev = v.device
+    pix = torch.empty((B, h, w), dtype=torch.int64, device=dev)
+    zbuf = torch.empty((B, h, w), dtype=_f32, device=dev)
+    bary = torch.empty((B, h, w, 3), dtype=_f32, device=dev)
+    out = torch.empty((B, C, h, w), dtype=_f32, device=dev)
+    ws = torch.empty(int(lib.mpf_rasterize_grid_workspace(B, h, w)) // 8, dtype=torch.int64, device=dev)
+    a = _lib.MpfMeshRasterArgs()
+    a.verts_ndc, a.attrs, a.pix_to_face, a.zbuf, a.bary, a.out = v.data_ptr(), at.data_ptr(), pix.data_ptr(), zbuf.data_ptr(), bary.data_ptr(), out.data_ptr()
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 8
+    a.B, a.h, a.w, a.C, a.blur_radius = B, h, w, C, blur
+    _lib.check(lib.mpf_rasterize_grid(ctypes.byref(a), _stream()), "mpf_rasterize_grid")
+    del ws
+    return pix, zbuf, bary, out
+
+
 def _check_out_int(t, who, dtype, shape, layout):
     """check_tensor's rule for an integer `out` (the float32 test replaced by `dtype`): type, dtype, shape, contiguity; the 4-byte alignment
     the kernels' dword stores need.  Returns t itself."""
