@@ -47,7 +47,8 @@ extern "C" {
                              mpf_adamw_workspace with MpfOptTensor / MpfAdamWArgs, and now mpf_forward_interpolate and
                              mpf_forward_interpolate_workspace with MpfWarmStartArgs, and now mpf_flow_to_image, mpf_flow_to_image_workspace and
                              mpf_flow_encode_kitti with MpfFlowVizArgs, and now mpf_rgbd_mesh_vertices, mpf_rasterize_grid and
-                             mpf_rasterize_grid_workspace with MpfMeshVertexArgs / MpfMeshRasterArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
+                             mpf_rasterize_grid_workspace with MpfMeshVertexArgs / MpfMeshRasterArgs, and now mpf_canny and mpf_canny_workspace
+                             with MpfCannyArgs and the four mpf_stage2_* calls with MpfStage2Args) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
 
 /* d_params layout (floats):
  *   [0..8]   K_src^-1 (3x3 row-major)            [9..20]  G_tgt_src rows 0..2 (3x4 row-major: R | t)
@@ -845,6 +846,73 @@ typedef struct MpfMeshRasterArgs {
 int mpf_rgbd_mesh_vertices(const MpfMeshVertexArgs *a, void *stream);
 size_t mpf_rasterize_grid_workspace(int B, int h, int w);   /* 0 for a shape the call refuses */
 int mpf_rasterize_grid(const MpfMeshRasterArgs *a, void *stream);
+
+/* Warp-back stage 2 (warpback/stage2_dataset.py): the masked Canny of get_edge on the device, and the pointwise chain of inpaint around the
+ * three EdgeConnect generators.  All tensors f32 and contiguous unless stated; every operation f32, rounded once, never contracted.
+ *   mpf_canny        skimage.feature.canny(gray, sigma, low_threshold, high_threshold, mask) per image of a batch, in three stages whose
+ *                    definition INTEGRATION.md section 17 states operation by operation (tests/canny_restated.py restates it):
+ *                      1  smoothed = G(mask ? gray : 0) / (G(mask ? 1 : 0) + FLT_EPSILON), G the separable Gaussian of `weights` (2 radius + 1
+ *                         taps, along the row index first, then along the column index, zero outside the image, taps added from -radius up)
+ *                      2  Sobel of smoothed under a reflected border, magnitude, and the class of every pixel: 0, or for a pixel of the
+ *                         3 x 3-eroded mask off the border ring whose magnitude is >= low_threshold and >= the two magnitudes interpolated
+ *                         along its gradient, 1 (weak) or 2 (strong: magnitude >= high_threshold)
+ *                      3  out = 1.0 where a weak or strong pixel is 8-connected through weak or strong pixels to a strong one, else 0.0
+ *                    The workspace keeps smoothed [B,h,w] f32 at offset 0 and the classes [B,h,w] u8 at offset 4 B h w; `passes` runs one
+ *                    stage alone on what the stage before left there.  Stage 3 is one workgroup per image sweeping a bit map (in LDS up to
+ *                    MPF_CANNY_LDS_WORDS words per plane, else in the workspace) to the fixpoint: at most h w sweeps, no workgroup waits
+ *                    for another, identical bytes on every run.  Class bytes other than 1 and 2 count as 0.
+ * Limits: B <= 65535; h, w >= 1; B * h * w <= MPF_CANNY_MAX_BHW; 0 <= radius <= MPF_CANNY_MAX_RADIUS; low_threshold <= high_threshold, no NaN.
+ * Validated before anything is launched (MPF_ERR_BAD_ARGUMENT); tensor VALUES are unrestricted: no address depends on one. */
+#define MPF_CANNY_MAX_RADIUS 16
+#define MPF_CANNY_MAX_BHW 268435456      /* 2^28 */
+#define MPF_CANNY_LDS_WORDS 6144         /* h * ceil(w / 32) up to which stage 3 keeps its two bit planes in LDS (48 KiB) */
+#define MPF_CANNY_PASS_ALL 0
+#define MPF_CANNY_PASS_SMOOTH 1          /* stage 1 only: gray, mask -> workspace (smoothed); out may be NULL */
+#define MPF_CANNY_PASS_CLASSIFY 2        /* stage 2 only: workspace (smoothed), mask -> workspace (classes); gray and out may be NULL */
+#define MPF_CANNY_PASS_HYSTERESIS 3      /* stage 3 only: workspace (classes) -> out; gray and mask may be NULL */
+typedef struct MpfCannyArgs {
+    const float *gray;               /* [B,1,h,w] */
+    const float *mask;               /* [B,1,h,w]: nonzero is inside */
+    float *out;                      /* [B,1,h,w], written: 0.0 or 1.0 */
+    void *workspace;                 /* mpf_canny_workspace(B, h, w) bytes, 4-byte aligned */
+    size_t workspace_bytes;
+    int B, h, w;
+    int radius;                      /* int(4 sigma + 0.5) */
+    float weights[2 * MPF_CANNY_MAX_RADIUS + 1];   /* weights[radius + k] = exp(-0.5 k^2 / sigma^2) / sum, formed in f64 on the host, rounded once */
+    float low_threshold, high_threshold;
+    int passes;                      /* MPF_CANNY_PASS_* */
+} MpfCannyArgs;
+size_t mpf_canny_workspace(int B, int h, int w);   /* 0 for a shape the call refuses */
+int mpf_canny(const MpfCannyArgs *a, void *stream);
+
+/*   mpf_stage2_*     inpaint's torch glue, one launch each, every result equal to the torch expression bit for bit:
+ *                      _gray_hole    gray = (0.2989 r + 0.587 g) + 0.114 b of image; mask_hole = 1 - mask
+ *                      _edge_input   edge_input [B,3,h,w] = (gray, edge, mask_hole)
+ *                      _gen_inputs   image_input [B,4,h,w] = (image + mask_hole per channel, edge_inpaint); disp_input [B,2,h,w] = (disp +
+ *                                    mask_hole, edge_inpaint)
+ *                      _merge        image_merged = image * (1 - mask_hole) + image_inpaint * mask_hole per channel; disp_merged likewise
+ *                    Each call reads and writes only the fields named for it; an output must not overlap an input.  B * h * w <= 2^28. */
+typedef struct MpfStage2Args {
+    const float *image;              /* [B,3,h,w] */
+    const float *disp;               /* [B,1,h,w] */
+    const float *mask;               /* [B,1,h,w] */
+    const float *edge;               /* [B,1,h,w] */
+    const float *edge_inpaint;       /* [B,1,h,w] */
+    const float *image_inpaint;      /* [B,3,h,w] */
+    const float *disp_inpaint;       /* [B,1,h,w] */
+    float *gray;                     /* [B,1,h,w]: written by _gray_hole, read by _edge_input */
+    float *mask_hole;                /* [B,1,h,w]: written by _gray_hole, read by the other three */
+    float *edge_input;               /* [B,3,h,w] */
+    float *image_input;              /* [B,4,h,w] */
+    float *disp_input;               /* [B,2,h,w] */
+    float *image_merged;             /* [B,3,h,w] */
+    float *disp_merged;              /* [B,1,h,w] */
+    int B, h, w;
+} MpfStage2Args;
+int mpf_stage2_gray_hole(const MpfStage2Args *a, void *stream);
+int mpf_stage2_edge_input(const MpfStage2Args *a, void *stream);
+int mpf_stage2_gen_inputs(const MpfStage2Args *a, void *stream);
+int mpf_stage2_merge(const MpfStage2Args *a, void *stream);
 
 /* The optimizer tail of RAFT/train.py (train.py:178-181: clip_grad_norm_, AdamW.step) over a whole parameter set, as one multi-tensor path:
  * the global gradient norm, the clip coefficient and torch's single-tensor AdamW update, without host synchronisation.  All tensors f32.

@@ -197,6 +197,25 @@ MESH_MAX_ATTRS = 8              # MPF_MESH_MAX_ATTRS
 MESH_PASS_ALL, MESH_PASS_Z, MESH_PASS_RESOLVE = 0, 1, 2    # MPF_MESH_PASS_*
 MESH_MAX_BHW = 1 << 28          # MPF_MESH_MAX_BHW
 
+CANNY_MAX_RADIUS = 16           # MPF_CANNY_MAX_RADIUS
+CANNY_MAX_BHW = 1 << 28         # MPF_CANNY_MAX_BHW
+CANNY_LDS_WORDS = 6144          # MPF_CANNY_LDS_WORDS
+CANNY_PASS_ALL, CANNY_PASS_SMOOTH, CANNY_PASS_CLASSIFY, CANNY_PASS_HYSTERESIS = 0, 1, 2, 3    # MPF_CANNY_PASS_*
+
+
+class MpfCannyArgs(ctypes.Structure):
+    """struct MpfCannyArgs of include/mpiflow_hip.h: warp-back stage 2's masked Canny (smoothing, classes, hysteresis), batched."""
+    _fields_ = [("gray", c_p), ("mask", c_p), ("out", c_p), ("workspace", c_p), ("workspace_bytes", c_sz), ("B", c_i), ("h", c_i), ("w", c_i),
+                ("radius", c_i), ("weights", c_f * (2 * CANNY_MAX_RADIUS + 1)), ("low_threshold", c_f), ("high_threshold", c_f), ("passes", c_i)]
+
+
+class MpfStage2Args(ctypes.Structure):
+    """struct MpfStage2Args of include/mpiflow_hip.h: the pointwise chain of warp-back stage 2's inpaint around the three generators."""
+    _fields_ = [("image", c_p), ("disp", c_p), ("mask", c_p), ("edge", c_p), ("edge_inpaint", c_p), ("image_inpaint", c_p), ("disp_inpaint", c_p),
+                ("gray", c_p), ("mask_hole", c_p), ("edge_input", c_p), ("image_input", c_p), ("disp_input", c_p), ("image_merged", c_p),
+                ("disp_merged", c_p), ("B", c_i), ("h", c_i), ("w", c_i)]
+
+
 WARM_MAX_HW = 65536             # MPF_WARM_MAX_HW
 WARM_MAX_NHW = 1 << 22          # MPF_WARM_MAX_NHW
 
@@ -301,6 +320,12 @@ SIGNATURES = {
     "mpf_rgbd_mesh_vertices": (c_i, [ctypes.POINTER(MpfMeshVertexArgs), c_p]),
     "mpf_rasterize_grid_workspace": (c_sz, [c_i, c_i, c_i]),
     "mpf_rasterize_grid": (c_i, [ctypes.POINTER(MpfMeshRasterArgs), c_p]),
+    "mpf_canny_workspace": (c_sz, [c_i, c_i, c_i]),
+    "mpf_canny": (c_i, [ctypes.POINTER(MpfCannyArgs), c_p]),
+    "mpf_stage2_gray_hole": (c_i, [ctypes.POINTER(MpfStage2Args), c_p]),
+    "mpf_stage2_edge_input": (c_i, [ctypes.POINTER(MpfStage2Args), c_p]),
+    "mpf_stage2_gen_inputs": (c_i, [ctypes.POINTER(MpfStage2Args), c_p]),
+    "mpf_stage2_merge": (c_i, [ctypes.POINTER(MpfStage2Args), c_p]),
     "mpf_adamw_workspace": (c_sz, [ctypes.POINTER(MpfOptTensor), c_i]),
     "mpf_grad_norm": (c_i, [ctypes.POINTER(MpfAdamWArgs), c_p]),
     "mpf_adamw_clipped": (c_i, [ctypes.POINTER(MpfAdamWArgs), c_p]),

@@ -1545,6 +1545,177 @@ def rasterize_grid(verts_ndc, attrs, h, w, blur_radius=1e-6):
     return pix, zbuf, bary, out
 
 
+CANNY_PASSES = {"all": _lib.CANNY_PASS_ALL, "smooth": _lib.CANNY_PASS_SMOOTH, "classify": _lib.CANNY_PASS_CLASSIFY, "hysteresis": _lib.CANNY_PASS_HYSTERESIS}
+
+
+def canny_weights(sigma):
+    """(radius, weights): the Gaussian taps of canny_masked, radius = int(4 sigma + 0.5) and w[radius + k] = exp(-0.5 / sigma^2 * k^2) over their
+    sum, formed in float64 (math.fsum) and rounded to float32 once; a list of 2 radius + 1 Python floats holding float32 values"""
+    import math
+    import struct
+    sigma = float(sigma)
+    radius = int(4.0 * sigma + 0.5)
+    phi = [math.exp(-0.5 / (sigma * sigma) * (k * k)) for k in range(-radius, radius + 1)]
+    total = math.fsum(phi)
+    return radius, [struct.unpack("f", struct.pack("f", p / total))[0] for p in phi]
+
+
+def canny_workspace(B, h, w, device):
+    """an uninitialised workspace for canny_masked on [B,1,h,w] (float32, mpf_canny_workspace bytes); canny_workspace_views names its parts"""
+    n = int(_lib.load().mpf_canny_workspace(int(B), int(h), int(w)))
+    if n == 0:
+        raise _lib.MpiFlowHipError("canny_workspace: B must be 1..65535, h, w >= 1 and B * h * w at most %d (got %r, %r, %r)" % (_lib.CANNY_MAX_BHW, B, h, w))
+    return torch.empty(n // 4, dtype=_f32, device=device)
+
+
+def canny_workspace_views(workspace, B, h, w):
+    """(smoothed float32 [B,1,h,w], classes uint8 [B,1,h,w]: 0, 1 weak, 2 strong): what the stages of canny_masked leave in a workspace, as views"""
+    n = B * h * w
+    return workspace[:n].view(B, 1, h, w), workspace.view(torch.uint8)[4 * n:5 * n].view(B, 1, h, w)
+
+
+@_on_device
+def canny_masked(gray, mask, sigma=2.0, low_threshold=0.1, high_threshold=0.2, out=None, workspace=None, passes="all"):
+    """mpf_canny: skimage.feature.canny(gray[i, 0], sigma, low_threshold, high_threshold, mask=mask[i, 0] != 0) for every image of gray
+    [b,1,h,w] with mask [b,1,h,w] (nonzero: inside) -> [b,1,h,w] float32 of 0.0 and 1.0, what the reference's get_edge returns.  Three
+    stages - the masked, normalised Gaussian; Sobel, magnitude and interpolated non-maximum suppression into classes; hysteresis as a
+    reachability fixpoint - in float32 exactly as INTEGRATION.md section 17 states them; identical bytes on every run.  `out`: a tensor to
+    write; `workspace`: canny_workspace(b, h, w, device), reused between calls; `passes`: 'all', or one stage alone on what the stage before
+    left in the workspace ('smooth' returns the smoothed view, 'classify' the class view of canny_workspace_views, 'hysteresis' out; the
+    last two need `workspace`).  float32, contiguous, on the GPU, or MpiFlowHipError.  Asynchronous on the current stream: no host copy, no
+    synchronisation."""
+    who = "canny_masked"
+    g = check_tensor(gray, "gray", who, (None, 1, None, None), "[b,1,h,w]")
+    B, _, h, w = g.shape
+    m = check_tensor(mask, "mask", who, (B, 1, h, w), "[b,1,h,w] like gray")
+    tensors = dict(gray=g, mask=m)
+    if out is not None:
+        tensors["out"] = check_tensor(out, "out", who, (B, 1, h, w), "[b,1,h,w] like gray")
+    if passes not in CANNY_PASSES:
+        raise _lib.MpiFlowHipError("%s: passes must be one of %s (got %r)" % (who, ", ".join(CANNY_PASSES), passes))
+    try:
+        sigma, lo, hi = float(sigma), float(low_threshold), float(high_threshold)
+    except (TypeError, ValueError):
+        raise _lib.MpiFlowHipError("%s: sigma, low_threshold and high_threshold must be numbers (got %r, %r, %r)" % (who, sigma, low_threshold, high_threshold)) from None
+    if not 0.0 < sigma < float("inf"):
+        raise _lib.MpiFlowHipError("%s: sigma must be a finite number > 0 (got %r)" % (who, sigma))
+    if int(4.0 * sigma + 0.5) > _lib.CANNY_MAX_RADIUS:
+        raise _lib.MpiFlowHipError("%s: sigma = %r needs a radius of int(4 sigma + 0.5) = %d taps, more than the %d the kernel holds"
+                                   % (who, sigma, int(4.0 * sigma + 0.5), _lib.CANNY_MAX_RADIUS))
+    if not lo <= hi:
+        raise _lib.MpiFlowHipError("%s: low_threshold must be at most high_threshold, neither NaN (got %r, %r)" % (who, low_threshold, high_threshold))
+    if B < 1 or h < 1 or w < 1 or B > 65535 or B * h * w > _lib.CANNY_MAX_BHW:
+        raise _lib.MpiFlowHipError("%s: gray must have 1..65535 images of at least one pixel and at most %d pixels in all (got shape %s)" % (who, _lib.CANNY_MAX_BHW, tuple(g.shape)))
+    lib = _lib.load()
+    need = int(lib.mpf_canny_workspace(B, h, w))
+    if workspace is not None:
+        ws = check_tensor(workspace, "workspace", who, 1)
+        if ws.numel() * 4 < need:
+            raise _lib.MpiFlowHipError("%s: workspace holds %d bytes, %d needed (ops.canny_workspace)" % (who, ws.numel() * 4, need))
+        tensors["workspace"] = ws
+    elif passes in ("classify", "hysteresis"):
+        raise _lib.MpiFlowHipError("%s: passes=%r reads what the stage before left in `workspace`: hand one in" % (who, passes))
+    check_devices(who, tensors)
+    ws = torch.empty(need // 4, dtype=_f32, device=g.device) if workspace is None else workspace
+    if out is None and passes in ("all", "hysteresis"):
+        out = torch.empty_like(g)
+    radius, weights = canny_weights(sigma)
+    a = _lib.MpfCannyArgs()
+    a.gray, a.mask, a.out = g.data_ptr(), m.data_ptr(), None if out is None else out.data_ptr()
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    a.B, a.h, a.w, a.radius = B, h, w, radius
+    for k, v in enumerate(weights):
+        a.weights[k] = v
+    a.low_threshold, a.high_threshold, a.passes = lo, hi, CANNY_PASSES[passes]
+    _lib.check(lib.mpf_canny(ctypes.byref(a), _stream()), "mpf_canny")
+    if passes == "smooth":
+        return canny_workspace_views(ws, B, h, w)[0]
+    if passes == "classify":
+        return canny_workspace_views(ws, B, h, w)[1]
+    return out
+
+
+def _stage2_args(who, B, h, w, **tensors):
+    """MpfStage2Args with the named fields set; every tensor already checked"""
+    if B < 1 or h < 1 or w < 1 or B > 65535 or B * h * w > (1 << 28):
+        raise _lib.MpiFlowHipError("%s: 1..65535 images of at least one pixel and at most 2^28 pixels in all (got B, h, w = %d, %d, %d)" % (who, B, h, w))
+    check_devices(who, tensors)
+    a = _lib.MpfStage2Args()
+    a.B, a.h, a.w = B, h, w
+    for name, t in tensors.items():
+        setattr(a, name, t.data_ptr())
+    return a
+
+
+def _stage2_out(t, name, who, shape, like):
+    return torch.empty(shape, dtype=_f32, device=like.device) if t is None else check_tensor(t, name, who, shape)
+
+
+@_on_device
+def stage2_gray_hole(image, mask):
+    """mpf_stage2_gray_hole: image [b,3,h,w], mask [b,1,h,w] -> (gray [b,1,h,w] = (0.2989 r + 0.587 g) + 0.114 b, torchvision's Grayscale;
+    mask_hole = 1 - mask), one launch, equal to the torch expressions bit for bit.  float32, contiguous, on the GPU, or MpiFlowHipError."""
+    who = "stage2_gray_hole"
+    img = check_tensor(image, "image", who, (None, 3, None, None), "[b,3,h,w]")
+    B, _, h, w = img.shape
+    m = check_tensor(mask, "mask", who, (B, 1, h, w), "[b,1,h,w] like image")
+    check_devices(who, dict(image=img, mask=m))
+    gray, hole = torch.empty_like(m), torch.empty_like(m)
+    a = _stage2_args(who, B, h, w, image=img, mask=m, gray=gray, mask_hole=hole)
+    _lib.check(_lib.load().mpf_stage2_gray_hole(ctypes.byref(a), _stream()), "mpf_stage2_gray_hole")
+    return gray, hole
+
+
+@_on_device
+def stage2_edge_input(gray, edge, mask_hole, out=None):
+    """mpf_stage2_edge_input: the edge generator's input cat([gray, edge, mask_hole], 1) [b,3,h,w], written straight into one buffer"""
+    who = "stage2_edge_input"
+    g = check_tensor(gray, "gray", who, (None, 1, None, None), "[b,1,h,w]")
+    B, _, h, w = g.shape
+    e = check_tensor(edge, "edge", who, (B, 1, h, w), "[b,1,h,w] like gray")
+    mh = check_tensor(mask_hole, "mask_hole", who, (B, 1, h, w), "[b,1,h,w] like gray")
+    out = _stage2_out(out, "out", who, (B, 3, h, w), g)
+    a = _stage2_args(who, B, h, w, gray=g, edge=e, mask_hole=mh, edge_input=out)
+    _lib.check(_lib.load().mpf_stage2_edge_input(ctypes.byref(a), _stream()), "mpf_stage2_edge_input")
+    return out
+
+
+@_on_device
+def stage2_gen_inputs(image, disp, mask_hole, edge_inpaint):
+    """mpf_stage2_gen_inputs: both inpainting generators' inputs in one launch: (cat([image + mask_hole, edge_inpaint], 1) [b,4,h,w],
+    cat([disp + mask_hole, edge_inpaint], 1) [b,2,h,w])"""
+    who = "stage2_gen_inputs"
+    img = check_tensor(image, "image", who, (None, 3, None, None), "[b,3,h,w]")
+    B, _, h, w = img.shape
+    d = check_tensor(disp, "disp", who, (B, 1, h, w), "[b,1,h,w] like image")
+    mh = check_tensor(mask_hole, "mask_hole", who, (B, 1, h, w), "[b,1,h,w] like image")
+    e = check_tensor(edge_inpaint, "edge_inpaint", who, (B, 1, h, w), "[b,1,h,w] like image")
+    check_devices(who, dict(image=img, disp=d, mask_hole=mh, edge_inpaint=e))
+    xi = torch.empty((B, 4, h, w), dtype=_f32, device=img.device)
+    xd = torch.empty((B, 2, h, w), dtype=_f32, device=img.device)
+    a = _stage2_args(who, B, h, w, image=img, disp=d, mask_hole=mh, edge_inpaint=e, image_input=xi, disp_input=xd)
+    _lib.check(_lib.load().mpf_stage2_gen_inputs(ctypes.byref(a), _stream()), "mpf_stage2_gen_inputs")
+    return xi, xd
+
+
+@_on_device
+def stage2_merge(image, image_inpaint, disp, disp_inpaint, mask_hole):
+    """mpf_stage2_merge: (image * (1 - mask_hole) + image_inpaint * mask_hole, disp * (1 - mask_hole) + disp_inpaint * mask_hole) in one launch,
+    in the reference's operation order: equal to the torch expressions bit for bit"""
+    who = "stage2_merge"
+    img = check_tensor(image, "image", who, (None, 3, None, None), "[b,3,h,w]")
+    B, _, h, w = img.shape
+    inp = check_tensor(image_inpaint, "image_inpaint", who, (B, 3, h, w), "[b,3,h,w] like image")
+    d = check_tensor(disp, "disp", who, (B, 1, h, w), "[b,1,h,w] like image")
+    dinp = check_tensor(disp_inpaint, "disp_inpaint", who, (B, 1, h, w), "[b,1,h,w] like image")
+    mh = check_tensor(mask_hole, "mask_hole", who, (B, 1, h, w), "[b,1,h,w] like image")
+    check_devices(who, dict(image=img, image_inpaint=inp, disp=d, disp_inpaint=dinp, mask_hole=mh))
+    oi, od = torch.empty_like(img), torch.empty_like(d)
+    a = _stage2_args(who, B, h, w, image=img, image_inpaint=inp, disp=d, disp_inpaint=dinp, mask_hole=mh, image_merged=oi, disp_merged=od)
+    _lib.check(_lib.load().mpf_stage2_merge(ctypes.byref(a), _stream()), "mpf_stage2_merge")
+    return oi, od
+
+
 def _check_out_int(t, who, dtype, shape, layout):
     """check_tensor's rule for an integer `out` (the float32 test replaced by `dtype`): type, dtype, shape, contiguity; the 4-byte alignment
     the kernels' dword stores need.  Returns t itself."""
