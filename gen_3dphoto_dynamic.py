@@ -84,6 +84,10 @@ def parse(argv=None):
                         "builtin = the same algorithm restated in libmpiflow_hip.so, run on the writer threads; ns-hip = builtin's NS fill on the GPU "
                         "(the same bytes as builtin, no host fill; parity with cv2 itself unpinned, as for builtin); peel (alias hip) = the "
                         "onion-peel GPU kernel, NOT OpenCV's algorithm; none = leave holes white")
+    p.add_argument("--disp-filter", type=str, default=None,
+                   help="windows of the sparse bilateral filter (3d-photo-inpainting's depth-edge sharpening, the call the reference keeps commented "
+                        "out in disparity_to_tensor), one iteration per window, e.g. 5,5; run on the GPU on every disparity at file resolution before "
+                        "the input stage.  Default: off (the reference's behaviour)")
     p.add_argument("--resume", action="store_true", help="skip images whose outputs (all --repeat pairs) already exist; the RNG schedule is unaffected")
     p.add_argument("--gpus", type=int, default=0,
                    help="GPUs of this node to shard the images over, one process per GPU (the reference's model: scripts/gen_train_kitti15_v2.sh "
@@ -241,7 +245,7 @@ def main(argv=None):
                 prof[self.key] = prof.get(self.key, 0.0) + time.perf_counter() - self.t
 
     model_dtype = opt.model_dtype if opt.model_engine == "hip" else None        # None: the torch modules under autocast `amp`
-    lanes = [producer.Lane(dev, opt.height, opt.width, opt.planes, model, model_dtype, amp, lap) for _ in range(max(1, opt.lanes))]
+    lanes = [producer.Lane(dev, opt.height, opt.width, opt.planes, model, model_dtype, amp, lap, disp_filter=opt.disp_filter) for _ in range(max(1, opt.lanes))]
     dstats = pipeline.DeviceStats(dev)
     ring = io_formats.OutputRing(opt.height, opt.width, dev, slots=max(4, 2 * max(opt.writers, 1)), threads=max(opt.writers, 1), host_fill=host_fill)
     t_start = time.perf_counter()

@@ -48,7 +48,8 @@ extern "C" {
                              mpf_forward_interpolate_workspace with MpfWarmStartArgs, and now mpf_flow_to_image, mpf_flow_to_image_workspace and
                              mpf_flow_encode_kitti with MpfFlowVizArgs, and now mpf_rgbd_mesh_vertices, mpf_rasterize_grid and
                              mpf_rasterize_grid_workspace with MpfMeshVertexArgs / MpfMeshRasterArgs, and now mpf_canny and mpf_canny_workspace
-                             with MpfCannyArgs and the four mpf_stage2_* calls with MpfStage2Args) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
+                             with MpfCannyArgs and the four mpf_stage2_* calls with MpfStage2Args, and now mpf_sparse_bilateral, mpf_sparse_bilateral_workspace
+                             and mpf_sparse_bilateral_rank with MpfBilateralArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
 
 /* d_params layout (floats):
  *   [0..8]   K_src^-1 (3x3 row-major)            [9..20]  G_tgt_src rows 0..2 (3x4 row-major: R | t)
@@ -913,6 +914,44 @@ int mpf_stage2_gray_hole(const MpfStage2Args *a, void *stream);
 int mpf_stage2_edge_input(const MpfStage2Args *a, void *stream);
 int mpf_stage2_gen_inputs(const MpfStage2Args *a, void *stream);
 int mpf_stage2_merge(const MpfStage2Args *a, void *stream);
+
+/* The sparse bilateral filter of 3d-photo-inpainting (the reference's bilateral_filter.py: sparse_bilateral_filtering): a 0/1-weighted median
+ * around disparity discontinuities, num_iter times, per image of a batch.  INTEGRATION.md section 18 states it operation by operation
+ * (tests/bilateral_restated.py restates it).  With v = depth, per iteration i, ws = filter_size[i], m = ws / 2:
+ *   1  D = 1 at interior pixels where |1 / v[p] - 1 / v[q]| > depth_threshold for one of the four neighbours q (with a mask: only where
+ *      mask[p] and mask[q] are both nonzero), 1 where the call's INPUT is 0, then 0 where the mask is 0.  The divide is correctly rounded;
+ *      inf and NaN take their IEEE course (NaN > t is false).
+ *   2  v' and D' are v and D with the outermost ring replaced by its inner neighbour, then edge-padded by m; the mask is zero-padded.
+ *   3  a pixel whose mask is 0, or whose ws x ws window holds no D', gets v'.  Another gets the k*(n)-th smallest of the n valid values
+ *      of its window (D' = 0 and mask nonzero), or v' when n = 0.  k*(n) = mpf_sparse_bilateral_rank(n): 1 + #{k <= n : S_k <= 0.5} with
+ *      S_k the f32 sum of k copies of fl32(1 / n) added one at a time, which is NOT n / 2 + 1 for every n.
+ * dtype: MPF_BILATERAL_F32 (arithmetic in f32, the threshold rounded to f32), _F64, or _U8, whose value is u / 255.0 in f64 and whose output
+ * is the selected pixel's byte.  The result is a selection of input values: identical bytes on every run, no atomics.  One call runs every
+ * iteration (two launches each), between two buffers of the workspace; the last iteration writes out.
+ * Limits: B <= 65535; h, w >= 3; B * h * w <= MPF_BILATERAL_MAX_BHW; 1 <= num_iter <= MPF_BILATERAL_MAX_ITER; filter_size[i] in 3, 5, 7, 9;
+ * depth_threshold not NaN.  Validated before anything is launched (MPF_ERR_BAD_ARGUMENT).  Values are meant to be finite; NaN is not looked for. */
+#define MPF_BILATERAL_F32 0
+#define MPF_BILATERAL_F64 1
+#define MPF_BILATERAL_U8 2
+#define MPF_BILATERAL_MAX_WINDOW 9
+#define MPF_BILATERAL_MAX_ITER 8
+#define MPF_BILATERAL_MAX_BHW 268435456  /* 2^28 */
+typedef struct MpfBilateralArgs {
+    const void *depth;               /* [B,h,w] of dtype */
+    const unsigned char *mask;       /* [B,h,w] u8, or [h,w] with mask_shared, nonzero is inside; NULL: no mask */
+    void *out;                       /* [B,h,w] of dtype, written; must not overlap depth */
+    void *workspace;                 /* mpf_sparse_bilateral_workspace(dtype, B, h, w) bytes, 16-byte aligned */
+    size_t workspace_bytes;
+    int dtype;                       /* MPF_BILATERAL_F32 / _F64 / _U8 */
+    int B, h, w;
+    int mask_shared;                 /* 1: one [h,w] mask for every image */
+    int num_iter;
+    int filter_size[MPF_BILATERAL_MAX_ITER];
+    double depth_threshold;
+} MpfBilateralArgs;
+size_t mpf_sparse_bilateral_workspace(int dtype, int B, int h, int w);   /* 0 for a dtype or shape the call refuses */
+int mpf_sparse_bilateral_rank(int n);                                    /* k*(n) for 1 <= n <= 81, else 0; host arithmetic, no GPU */
+int mpf_sparse_bilateral(const MpfBilateralArgs *a, void *stream);
 
 /* The optimizer tail of RAFT/train.py (train.py:178-181: clip_grad_norm_, AdamW.step) over a whole parameter set, as one multi-tensor path:
  * the global gradient norm, the clip coefficient and torch's single-tensor AdamW update, without host synchronisation.  All tensors f32.

@@ -216,6 +216,18 @@ class MpfStage2Args(ctypes.Structure):
                 ("disp_merged", c_p), ("B", c_i), ("h", c_i), ("w", c_i)]
 
 
+BILATERAL_F32, BILATERAL_F64, BILATERAL_U8 = 0, 1, 2    # MPF_BILATERAL_F32 / _F64 / _U8
+BILATERAL_MAX_WINDOW = 9        # MPF_BILATERAL_MAX_WINDOW
+BILATERAL_MAX_ITER = 8          # MPF_BILATERAL_MAX_ITER
+BILATERAL_MAX_BHW = 1 << 28     # MPF_BILATERAL_MAX_BHW
+
+
+class MpfBilateralArgs(ctypes.Structure):
+    """struct MpfBilateralArgs of include/mpiflow_hip.h: the sparse bilateral filter (a 0/1-weighted median around discontinuities), batched."""
+    _fields_ = [("depth", c_p), ("mask", c_p), ("out", c_p), ("workspace", c_p), ("workspace_bytes", c_sz), ("dtype", c_i), ("B", c_i), ("h", c_i),
+                ("w", c_i), ("mask_shared", c_i), ("num_iter", c_i), ("filter_size", c_i * BILATERAL_MAX_ITER), ("depth_threshold", ctypes.c_double)]
+
+
 WARM_MAX_HW = 65536             # MPF_WARM_MAX_HW
 WARM_MAX_NHW = 1 << 22          # MPF_WARM_MAX_NHW
 
@@ -326,6 +338,9 @@ SIGNATURES = {
     "mpf_stage2_edge_input": (c_i, [ctypes.POINTER(MpfStage2Args), c_p]),
     "mpf_stage2_gen_inputs": (c_i, [ctypes.POINTER(MpfStage2Args), c_p]),
     "mpf_stage2_merge": (c_i, [ctypes.POINTER(MpfStage2Args), c_p]),
+    "mpf_sparse_bilateral_workspace": (c_sz, [c_i, c_i, c_i, c_i]),
+    "mpf_sparse_bilateral_rank": (c_i, [c_i]),
+    "mpf_sparse_bilateral": (c_i, [ctypes.POINTER(MpfBilateralArgs), c_p]),
     "mpf_adamw_workspace": (c_sz, [ctypes.POINTER(MpfOptTensor), c_i]),
     "mpf_grad_norm": (c_i, [ctypes.POINTER(MpfAdamWArgs), c_p]),
     "mpf_adamw_clipped": (c_i, [ctypes.POINTER(MpfAdamWArgs), c_p]),

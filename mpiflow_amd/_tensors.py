@@ -10,11 +10,15 @@ import torch
 from ._lib import CORR_MAX_LEVELS, MpiFlowHipError
 
 
-def check_tensor(t, name, who, shape, layout=None):
-    """`shape`: a tuple whose None entries are free, or just a rank; `layout`: a word for the message, such as "[N,C,H,W]".  Returns t itself."""
+def check_tensor(t, name, who, shape, layout=None, dtypes=None):
+    """`shape`: a tuple whose None entries are free, or just a rank; `layout`: a word for the message, such as "[N,C,H,W]"; `dtypes`: the
+    dtypes a call with kernels for several takes (default: float32 alone).  Returns t itself."""
     if not isinstance(t, torch.Tensor):
         raise MpiFlowHipError("%s: %s must be a torch.Tensor (got %s)" % (who, name, type(t).__name__))
-    if t.dtype != torch.float32:
+    if dtypes is not None:
+        if t.dtype not in dtypes:
+            raise MpiFlowHipError("%s: %s must be %s (got %s)" % (who, name, " or ".join(str(d).replace("torch.", "") for d in dtypes), t.dtype))
+    elif t.dtype != torch.float32:
         raise MpiFlowHipError("%s: %s must be float32 (got %s); call .float() on it (the kernels are float32 only)" % (who, name, t.dtype))
     rank, shape = (shape, ()) if isinstance(shape, int) else (len(shape), shape)
     if t.dim() != rank or any(s is not None and s != d for s, d in zip(shape, t.shape)):

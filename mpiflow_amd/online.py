@@ -217,12 +217,14 @@ class OnlinePairs:
     flow through KITTI's 16-bit code (quantize), nearest-pixel flow resize with holes, h-flip only, margin crop; augment= then takes only
     SPARSE_AUGMENT_KEYS (RAFT_KITTI_AUGMENT is the KITTI stage's), and photometric=True means RAFT_SPARSE_PHOTOMETRIC.
     mix: shuffle-buffer size in pairs (0 = off).  prefetch: batches enqueued ahead of the consumer.  rank / world_size: default from
-    torch.distributed or RANK / WORLD_SIZE.  fill_threads: host threads of fill="builtin" (default: default_fill_threads())."""
+    torch.distributed or RANK / WORLD_SIZE.  fill_threads: host threads of fill="builtin" (default: default_fill_threads()).
+    disp_filter: None = none, or the windows of the sparse bilateral filter, such as (5, 5), run on every disparity before the input stage
+    (the CLI's --disp-filter)."""
 
     def __init__(self, base, batch_size=8, crop=(288, 960), width=1280, height=384, seed=114514, ext_cz=0.15, pairs_per_image=5, poses="v2",
                  mpi_from="model", ckpt_path=None, model_dtype="auto", fill="auto", augment=dict(min_scale=-0.2, max_scale=0.5, do_flip=True),
                  shuffle=True, mix=32, prefetch=2, rank=None, world_size=None, device=None, planes=64, fill_threads=None, photometric=None,
-                 sparse=None):
+                 sparse=None, disp_filter=None):
         if torch.utils.data.get_worker_info() is not None:
             raise RuntimeError("OnlinePairs renders on the GPU in the training process: construct it there, not inside a DataLoader worker")
         if mpi_from not in ("model", "npz", "disparity"):
@@ -237,6 +239,7 @@ class OnlinePairs:
         self.mpi_from, self.augment, self.shuffle, self.mix, self.prefetch = mpi_from, (None if augment is None else dict(augment)), shuffle, int(mix), int(prefetch)
         self.sparse = sparse_config(sparse, self.augment)
         self.photometric = photometric_config(photometric, sparse=self.sparse is not None)
+        self.disp_filter = producer.parse_disp_filter(disp_filter)
         if rank is None or world_size is None:
             import torch.distributed as dist
             if dist.is_available() and dist.is_initialized():
@@ -307,7 +310,7 @@ class OnlinePairs:
                 with torch.cuda.stream(self.stream):
                     model = producer.load_model(ckpt_path, self.W, self.H, self.planes, dev)
                 self.planes = model.num_planes
-            self.lane = producer.Lane(dev, self.H, self.W, self.planes, model, model_dtype, streams=(self.stream, self.tail))
+            self.lane = producer.Lane(dev, self.H, self.W, self.planes, model, model_dtype, streams=(self.stream, self.tail), disp_filter=self.disp_filter)
             if model is not None and model_dtype in ("auto", "fp16"):
                 # capture the network's graph here, on the constructing thread, not in the producer while other threads use the device
                 with torch.cuda.stream(self.stream):

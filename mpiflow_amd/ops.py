@@ -1635,6 +1635,100 @@ def canny_masked(gray, mask, sigma=2.0, low_threshold=0.1, high_threshold=0.2, o
     return out
 
 
+BILATERAL_DTYPES = {torch.float32: _lib.BILATERAL_F32, torch.float64: _lib.BILATERAL_F64, torch.uint8: _lib.BILATERAL_U8}
+
+
+def sparse_bilateral_rank(n):
+    """k*(n), the rank sparse_bilateral_filter takes among n valid samples: 1 + #{k <= n : S_k <= 0.5}, S_k the float32 sum of k copies of
+    fl32(1 / n) added one at a time (the library's host arithmetic, the kernel's own function; no GPU)"""
+    k = int(_lib.load().mpf_sparse_bilateral_rank(int(n)))
+    if k == 0:
+        raise _lib.MpiFlowHipError("sparse_bilateral_rank: n must be 1..%d (got %r)" % (_lib.BILATERAL_MAX_WINDOW ** 2, n))
+    return k
+
+
+def sparse_bilateral_workspace(dtype, B, h, w, device):
+    """an uninitialised workspace for sparse_bilateral_filter on B images of h x w of `dtype` (uint8, mpf_sparse_bilateral_workspace bytes)"""
+    n = int(_lib.load().mpf_sparse_bilateral_workspace(BILATERAL_DTYPES.get(dtype, -1), int(B), int(h), int(w)))
+    if n == 0:
+        raise _lib.MpiFlowHipError("sparse_bilateral_workspace: dtype must be float32, float64 or uint8, B 1..65535, h, w >= 3 and B * h * w at most %d "
+                                   "(got %r, %r, %r, %r)" % (_lib.BILATERAL_MAX_BHW, dtype, B, h, w))
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+@_on_device
+def sparse_bilateral_filter(depth, filter_size, depth_threshold=0.04, mask=None, num_iter=None, out=None, workspace=None):
+    """mpf_sparse_bilateral: the reference's sparse_bilateral_filtering(depth, filter_size, depth_threshold=, mask=, num_iter=) per image of
+    depth [h,w], [B,h,w] or [B,1,h,w] -> a tensor like depth.  A 0/1-weighted median around disparity discontinuities, num_iter times
+    (None: len(filter_size)) with windows filter_size[i] in 3, 5, 7, 9, as INTEGRATION.md section 18 states it; the result is a selection of
+    input values, equal to the reference's bit for bit, identical bytes on every run.  depth: float32 (arithmetic in float32), float64, or
+    uint8, whose value is u / 255.0 in float64 (cv2.imread(path, 0) / 255) and whose result is the selected pixel's byte.  mask: bool, uint8
+    or float32 of 0 / 1, shaped like depth or [h,w] for every image.  `out`: a tensor like depth to write (not depth itself); `workspace`:
+    sparse_bilateral_workspace(...), reused between calls.  Contiguous, on the GPU, or MpiFlowHipError.  Asynchronous on the current stream."""
+    who = "sparse_bilateral_filter"
+    d = check_tensor(depth, "depth", who, depth.dim() if isinstance(depth, torch.Tensor) and depth.dim() in (2, 3, 4) else 3,
+                     "[h,w], [B,h,w] or [B,1,h,w]", dtypes=tuple(BILATERAL_DTYPES))
+    if d.dim() == 4 and d.shape[1] != 1:
+        raise _lib.MpiFlowHipError("%s: depth must be [h,w], [B,h,w] or [B,1,h,w], a contiguous tensor (got shape %s)" % (who, tuple(d.shape)))
+    B, (h, w) = (1 if d.dim() == 2 else d.shape[0]), d.shape[-2:]
+    tensors = dict(depth=d)
+    m = None
+    if mask is not None:
+        shared = isinstance(mask, torch.Tensor) and mask.dim() == 2 and d.dim() != 2
+        m = check_tensor(mask, "mask", who, (h, w) if shared else tuple(d.shape), "[h,w] or shaped like depth", dtypes=(torch.bool, torch.uint8, torch.float32))
+        tensors["mask"] = m
+    if out is not None:
+        tensors["out"] = check_tensor(out, "out", who, tuple(d.shape), "shaped like depth", dtypes=(d.dtype,))
+    try:
+        sizes = [operator.index(s) for s in filter_size]
+    except TypeError:
+        raise _lib.MpiFlowHipError("%s: filter_size must be a sequence of integers (got %r)" % (who, filter_size)) from None
+    for s in sizes:
+        if s % 2 == 0:
+            raise _lib.MpiFlowHipError("%s: a window must be odd (got %d in filter_size %r)" % (who, s, list(sizes)))
+        if not 3 <= s <= _lib.BILATERAL_MAX_WINDOW:
+            raise _lib.MpiFlowHipError("%s: a window must be 3, 5, 7 or 9 (got %d in filter_size %r)" % (who, s, list(sizes)))
+    if h < 3 or w < 3:
+        raise _lib.MpiFlowHipError("%s: depth must have at least 3 rows and 3 columns (got h, w = %d, %d)" % (who, h, w))
+    n_iter = len(sizes) if num_iter is None else operator.index(num_iter)
+    if n_iter > len(sizes):
+        raise _lib.MpiFlowHipError("%s: num_iter = %d needs %d windows, filter_size holds %d" % (who, n_iter, n_iter, len(sizes)))
+    if not 1 <= n_iter <= _lib.BILATERAL_MAX_ITER:
+        raise _lib.MpiFlowHipError("%s: num_iter must be 1..%d (got %d)" % (who, _lib.BILATERAL_MAX_ITER, n_iter))
+    thr = float(depth_threshold)
+    if thr != thr:
+        raise _lib.MpiFlowHipError("%s: depth_threshold must not be NaN" % who)
+    if B < 1 or B > 65535 or B * h * w > _lib.BILATERAL_MAX_BHW:
+        raise _lib.MpiFlowHipError("%s: depth must have 1..65535 images and at most %d pixels in all (got shape %s)" % (who, _lib.BILATERAL_MAX_BHW, tuple(d.shape)))
+    if out is not None and out.data_ptr() == d.data_ptr():
+        raise _lib.MpiFlowHipError("%s: out must not be depth itself (a pixel reads its neighbours)" % who)
+    lib = _lib.load()
+    code = BILATERAL_DTYPES[d.dtype]
+    need = int(lib.mpf_sparse_bilateral_workspace(code, B, h, w))
+    if workspace is not None:
+        ws = check_tensor(workspace, "workspace", who, 1, dtypes=(torch.uint8,))
+        if ws.numel() < need:
+            raise _lib.MpiFlowHipError("%s: workspace holds %d bytes, %d needed (ops.sparse_bilateral_workspace)" % (who, ws.numel(), need))
+        tensors["workspace"] = ws
+    check_devices(who, tensors)
+    ws = torch.empty(need, dtype=torch.uint8, device=d.device) if workspace is None else workspace
+    if out is None:
+        out = torch.empty_like(d)
+    if m is not None:                                                       # the kernel reads bytes: bool as it is, the others as != 0
+        m8 = m.view(torch.uint8) if m.dtype == torch.bool else (m if m.dtype == torch.uint8 else (m != 0).view(torch.uint8))
+    a = _lib.MpfBilateralArgs()
+    a.depth, a.mask, a.out = d.data_ptr(), None if m is None else m8.data_ptr(), out.data_ptr()
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    a.dtype, a.B, a.h, a.w = code, B, h, w
+    a.mask_shared = 1 if m is not None and m.dim() == 2 else 0
+    a.num_iter, a.depth_threshold = n_iter, thr
+    for i in range(n_iter):
+        a.filter_size[i] = sizes[i]
+    _lib.check(lib.mpf_sparse_bilateral(ctypes.byref(a), _stream()), "mpf_sparse_bilateral")
+    del ws
+    return out
+
+
 def _stage2_args(who, B, h, w, **tensors):
     """MpfStage2Args with the named fields set; every tensor already checked"""
     if B < 1 or h < 1 or w < 1 or B > 65535 or B * h * w > (1 << 28):

@@ -22,6 +22,20 @@ def intrinsics(W, H):
     return K.unsqueeze(0)
 
 
+def parse_disp_filter(disp_filter):
+    """disp_filter= of Lane / OnlinePairs and --disp-filter of the CLI: None, "5,5" or a sequence of windows -> None or a tuple of odd
+    windows in 3..9 (ops.sparse_bilateral_filter runs one iteration per window)."""
+    if disp_filter is None or disp_filter == "" or disp_filter is False:
+        return None
+    try:
+        sizes = tuple(int(s) for s in (disp_filter.split(",") if isinstance(disp_filter, str) else disp_filter))
+    except (TypeError, ValueError):
+        raise ValueError("disp_filter must be windows such as 5,5 (got %r)" % (disp_filter,)) from None
+    if not sizes or any(s not in (3, 5, 7, 9) for s in sizes) or len(sizes) > _lib.BILATERAL_MAX_ITER:
+        raise ValueError("disp_filter must be 1..%d windows, each 3, 5, 7 or 9 (got %r)" % (_lib.BILATERAL_MAX_ITER, disp_filter))
+    return sizes
+
+
 def mpi_from_disparity(image_3HW, disp_HW, S):
     """Stand-in MPI producer (--mpi-from disparity): colours on every plane, sigma = 1e-4 except 50 on the plane nearest to the pixel's
     disparity (a hard depth assignment).  Returns (mpi [S,4,H,W], disparity [S])."""
@@ -92,11 +106,13 @@ class Lane:
 
     model_dtype: the HIP engine make_predictor builds for `model`; None runs `model` as torch modules under autocast `amp`.  lap(label): a
     context factory timing the stages (no-op by default).  streams: (render, tail) streams the caller created, default two new ones.
-    front() and pairs() enqueue on the current stream: call them inside torch.cuda.stream(lane.stream)."""
+    disp_filter: None, or the windows of ops.sparse_bilateral_filter (such as (5, 5)), run on the uploaded disparity bytes at file
+    resolution before the input stage.  front() and pairs() enqueue on the current stream: call them inside torch.cuda.stream(lane.stream)."""
 
-    def __init__(self, device, H, W, planes, model=None, model_dtype=None, amp=None, lap=contextlib.nullcontext, streams=None):
+    def __init__(self, device, H, W, planes, model=None, model_dtype=None, amp=None, lap=contextlib.nullcontext, streams=None, disp_filter=None):
         self.device, self.H, self.W, self.planes, self.K = device, H, W, planes, intrinsics(W, H)
         self.model, self.amp, self.lap = model, amp, lap
+        self.disp_filter = parse_disp_filter(disp_filter)
         self.stream, self.tail_stream = streams or (torch.cuda.Stream(device=device), torch.cuda.Stream(device=device))
         self.stream.wait_stream(torch.cuda.current_stream(device))
         with torch.cuda.stream(self.stream):
@@ -122,6 +138,8 @@ class Lane:
             rgb8 = item["rgb_u8"].to(dev, non_blocking=True)
             dsp8 = item["disp_u8"].to(dev, non_blocking=True)
             ids = item["ids_u8"].to(dev, non_blocking=True)
+            if self.disp_filter is not None:
+                dsp8 = ops.sparse_bilateral_filter(dsp8.contiguous(), self.disp_filter)
             if rgb8.shape[:2] == dsp8.shape[:2]:
                 pre = ops.prepare_inputs(rgb_u8=rgb8, disp_u8=dsp8, size=(H, W), out=self.inputs)     # :82-89 in one launch
             else:                                                          # files of different sizes: each resized on its own, as :86-89 does

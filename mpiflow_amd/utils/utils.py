@@ -23,10 +23,16 @@ def image_to_tensor(img_path, unsqueeze=True):
     return rgb.unsqueeze(0) if unsqueeze else rgb
 
 
-def disparity_to_tensor(disp_path, unsqueeze=True):
-    """grey-scale disparity file -> [1,1,h,w] float in [0,1]   (reference :42-52; cv2.imread(path, 0) / 255)"""
+def disparity_to_tensor(disp_path, unsqueeze=True, filter_size=None, num_iter=None):
+    """grey-scale disparity file -> [1,1,h,w] float in [0,1]   (reference :42-52; cv2.imread(path, 0) / 255)
+    filter_size (off by default): the line the reference keeps commented out at :48, sparse_bilateral_filtering(disp, filter_size=[5, 5],
+    num_iter=2), live - on the GPU, on the file's bytes, whose filtered bytes / 255 are that call's float64 result bit for bit."""
     from ..io_formats import read_disparity_u8
-    disp = read_disparity_u8(disp_path).astype(np.float64) / 255      # 16-bit files: high byte, as cv2 - not PIL's saturating convert("L")
+    disp = read_disparity_u8(disp_path)                               # 16-bit files: high byte, as cv2 - not PIL's saturating convert("L")
+    if filter_size is not None:
+        from ..bilateral_filter import sparse_bilateral_filtering
+        disp = sparse_bilateral_filtering(disp, filter_size=filter_size, num_iter=num_iter)
+    disp = disp.astype(np.float64) / 255
     disp = torch.from_numpy(disp)[None, ...]
     if unsqueeze:
         disp = disp.unsqueeze(0)

@@ -12,6 +12,7 @@ import torch.nn.functional as F
 from torch.utils.data.dataloader import default_collate
 from torch.utils.data.dataset import Dataset
 
+from .. import ops
 from .utils import RGBDRenderer, disparity_to_tensor, image_to_tensor, transformation_from_parameters
 
 
@@ -30,8 +31,9 @@ def warp_back(image, disp, cam_int, cam_ext, cam_ext_inv, renderer=None):
 
 class WarpBackStage1Dataset(Dataset):
     def __init__(self, data_root, width=384, height=256, depth_dir_name="dpt_depth", device="cuda",
-                 trans_range={"x": 0.2, "y": -1, "z": -1, "a": -1, "b": -1, "c": -1}):
+                 trans_range={"x": 0.2, "y": -1, "z": -1, "a": -1, "b": -1, "c": -1}, disp_filter=None):
         self.data_root = data_root
+        self.disp_filter = disp_filter         # the one keyword the reference lacks: windows of ops.sparse_bilateral_filter, None = off
         self.depth_dir_name = depth_dir_name
         self.renderer = RGBDRenderer(device)
         self.width = width
@@ -77,10 +79,15 @@ class WarpBackStage1Dataset(Dataset):
         sign = 2 * (torch.randn_like(rand) > 0).float() - 1
         return sign * (r / 2 + r / 2 * rand)
 
+    def filter_disp(self, disp):
+        """preprocess_rgbd's note, "filter the depth map to reduce artifacts around depth discontinuities": the sparse bilateral filter on
+        the uploaded [b,1,h,w] disparity, once, where disp_filter asks for it"""
+        return disp if self.disp_filter is None else ops.sparse_bilateral_filter(disp.contiguous(), self.disp_filter)
+
     def collect_data(self, batch):
         image, disp = default_collate(batch)
         image = image.to(self.device)
-        disp = disp.to(self.device)
+        disp = self.filter_disp(disp.to(self.device))
         b = image.shape[0]
         cam_int = self.K.repeat(b, 1, 1)
         cam_ext, cam_ext_inv = self.get_rand_ext(b)

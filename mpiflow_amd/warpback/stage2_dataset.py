@@ -50,8 +50,10 @@ def warp_and_inpaint(image, disp, cam_int, cam_ext, cam_ext_inv, models, rendere
 
 class WarpBackStage2Dataset(WarpBackStage1Dataset):
     def __init__(self, data_root, width=384, height=256, depth_dir_name="dpt_depth", device="cuda",
-                 trans_range={"x": 0.2, "y": -1, "z": -1, "a": -1, "b": -1, "c": -1}, ec_weight_dir="warpback/ecweight", models=None):
-        super().__init__(data_root, width=width, height=height, depth_dir_name=depth_dir_name, device=device, trans_range=trans_range)
+                 trans_range={"x": 0.2, "y": -1, "z": -1, "a": -1, "b": -1, "c": -1}, ec_weight_dir="warpback/ecweight", models=None,
+                 disp_filter=None):
+        super().__init__(data_root, width=width, height=height, depth_dir_name=depth_dir_name, device=device, trans_range=trans_range,
+                         disp_filter=disp_filter)
         if models is None:
             models = get_edge_connect(ec_weight_dir)              # FileNotFoundError naming the three files it looked for
         self.edge_model, self.inpaint_model, self.disp_model = (m.to(self.device).eval() for m in models)
@@ -65,7 +67,7 @@ class WarpBackStage2Dataset(WarpBackStage1Dataset):
     def collect_data(self, batch):
         image, disp = default_collate(batch)
         image = image.to(self.device)
-        disp = disp.to(self.device)
+        disp = self.filter_disp(disp.to(self.device))
         b = image.shape[0]
         cam_int = self.K.repeat(b, 1, 1)
         cam_ext, cam_ext_inv = self.get_rand_ext(b)
