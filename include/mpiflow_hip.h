@@ -136,6 +136,13 @@ int mpf_warp_composite(const float *d_rgba, int interleaved, const float *d_mask
 int mpf_warp_composite_split(const float *d_rgb_S3HW, const float *d_sigma_SHW, const float *d_mask_quads, const float *d_params,
                              int S, int H, int W, float *d_rgb, float *d_depth, float *d_objmask, float *d_tgt_mask,
                              uint8_t *d_rgb_u8_bgr, void *stream);
+/* Adjoint of mpf_warp_composite_split with respect to the rgb and sigma stacks (same d_params and mask quads as the forward call).  Upstream
+ * gradients g_rgb [3,H,W], g_depth [H,W] (NULL ok), g_objmask [H,W] (NULL ok; needs the quads); tgt_mask has none.  Per target pixel: the forward's
+ * recurrence again, a back-to-front scan, and each plane's gradient scattered through its taps with float atomic adds into grad_rgb [S,3,H,W] and
+ * grad_sigma [S,H,W], which must be zero-initialised; nothing [S,C,H,W]-shaped exists in between.  Last bits depend on the order of the adds. */
+int mpf_warp_composite_bwd(const float *d_rgb_S3HW, const float *d_sigma_SHW, const float *d_mask_quads, const float *d_params, int S, int H, int W,
+                           const float *d_g_rgb, const float *d_g_depth, const float *d_g_objmask, float *d_grad_rgb_S3HW, float *d_grad_sigma_SHW,
+                           void *stream);
 
 /* Stage C alone on a bare sigma tensor [S,H,W]: the volume-rendered flows of P = 1 or 2 poses (HomographySample.sample_inverse,
  * utils/mpi/homography_sampler.py:160-220, + plane_volume_rendering_flow, utils/mpi/mpi_rendering.py:102-139) - what
@@ -1039,6 +1046,18 @@ int mpf_homography_flow(const float *d_params, int S, int H, int W, float *d_flo
 int mpf_volume_render(const float *d_rgb, const float *d_sigma, const float *d_xyz, int S, int64_t N,
                       float *d_rgb_out, float *d_depth_out, float *d_tacc_out, float *d_weights_out,
                       const float *d_extra_in, int E, float *d_extra_out, int hard, void *stream);
+/* Adjoint of mpf_volume_render with respect to rgb, sigma and the extras (xyz is constant).  Upstream gradients, each NULL when its output was not
+ * used: g_rgb [3,N], g_depth [N], g_extra [E,N], g_weights [S,N], g_tacc [S,N].  Results: grad_rgb [S,3,N] (NULL ok), grad_sigma [S,N] (required: it
+ * is also the kernel's only S-deep scratch), grad_extra [S,E,N] (NULL ok); every element is written, none needs initialising.  Two passes over the
+ * planes per pixel, t / A / w recomputed with the forward's own helpers.  d_rgb == NULL: the flow form.  hard != 0 (flow form only): grad_extra goes to
+ * the arg-max plane's values alone and grad_sigma is zero, as in torch, where the one-hot selection is constant. */
+int mpf_volume_render_bwd(const float *d_rgb, const float *d_sigma, const float *d_xyz, const float *d_extra_in, int S, int64_t N, int E, int hard,
+                          const float *d_g_rgb, const float *d_g_depth, const float *d_g_extra, const float *d_g_weights, const float *d_g_tacc,
+                          float *d_grad_rgb, float *d_grad_sigma, float *d_grad_extra, void *stream);
+/* Adjoint of mpf_homography_sample with respect to src, for the channels [c0, c1): g_src [S,C,H,W] += weight * g_tgt [S,C,H,W] through the taps the
+ * forward read (same d_params), as float atomic adds: d_g_src must be zero-initialised (or hold a sum to add to), channels outside the range are not
+ * touched, and the last bits of the result depend on the order in which the adds arrive.  valid and flowB2A have no gradient. */
+int mpf_homography_sample_bwd(const float *d_g_tgt, const float *d_params, int S, int C, int H, int W, int c0, int c1, float *d_g_src, void *stream);
 
 /* weighted_sum_mpi's sums with caller-supplied weights (utils/mpi/mpi_rendering.py:143-152):
  * out[c,n] = cascade-sum_s weights[s,n] * values[s,c,n]   (values NULL: plain sum of the weights, C must be 1) */

@@ -349,6 +349,9 @@ SIGNATURES = {
     "mpf_homography_sample": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
     "mpf_homography_flow": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
     "mpf_volume_render": (c_i, [c_p, c_p, c_p, c_i, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p]),
+    "mpf_volume_render_bwd": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i64, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "mpf_homography_sample_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
+    "mpf_warp_composite_bwd": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "mpf_weighted_sum": (c_i, [c_p, c_p, c_i, c_i, c_i64, c_p, c_p]),
     "mpf_alpha_composite": (c_i, [c_p, c_p, c_i, c_i, c_i64, c_p, c_p, c_p, c_p]),
     "mpf_disp_to_depth": (c_i, [c_p, c_i64, c_p, c_p]),

@@ -232,6 +232,37 @@ def warp_composite_split(rgb_S3HW, sigma_S1HW, quads, H_src_tgt=None, K_inv=None
     return dict(rgb=rgb, depth=depth, objmask=om, tgt_mask=tm, rgb_u8=u8)
 
 
+def _grad_buffer(t, name, shape, device, zero):
+    """A gradient tensor the backward kernels write in place: the caller's (fp32, contiguous, of this shape, on this device) or a new one."""
+    if t is None:
+        return (torch.zeros if zero else torch.empty)(shape, dtype=_f32, device=device)
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == device and t.dtype == _f32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise _lib.MpiFlowHipError("%s must be a contiguous float32 tensor of shape %s on %s" % (name, tuple(shape), device))
+    return t
+
+
+@_on_device
+def warp_composite_split_backward(rgb_S3HW, sigma_S1HW, quads, dparams, g_rgb, g_depth=None, g_objmask=None, grad_rgb=None, grad_sigma=None):
+    """Adjoint of warp_composite_split with respect to the two stacks (mpf_warp_composite_bwd): the same rgb, sigma, quads and dparams as the forward
+    call, the upstream gradients of rgb [3,H,W], depth [H,W] | None and objmask [H,W] | None.  -> (grad_rgb [S,3,H,W], grad_sigma [S,H,W]).  The kernel
+    ADDS into grad_rgb / grad_sigma with float atomics: pass zero-initialised buffers (or none: they are allocated zeroed).  The order in which the adds
+    arrive decides the last bits of each sum, so two runs may differ there."""
+    lib = _lib.load()
+    rgb_in = _dev(rgb_S3HW, "rgb stack")
+    S, C, H, W = rgb_in.shape
+    assert C == 3
+    sig = _dev(sigma_S1HW, "sigma stack").reshape(S, H, W)
+    q = _dev(quads, "mask quads") if quads is not None else None
+    gr = _dev(g_rgb, "g_rgb").reshape(3, H, W)
+    gd = _dev(g_depth, "g_depth").reshape(H, W) if g_depth is not None else None
+    gm = _dev(g_objmask, "g_objmask").reshape(H, W) if g_objmask is not None else None
+    grad_rgb = _grad_buffer(grad_rgb, "grad_rgb", (S, 3, H, W), rgb_in.device, True)
+    grad_sigma = _grad_buffer(grad_sigma, "grad_sigma", (S, H, W), rgb_in.device, True)
+    _lib.check(lib.mpf_warp_composite_bwd(_ptr(rgb_in), _ptr(sig), _ptr(q), _ptr(dparams), S, H, W, _ptr(gr), _ptr(gd), _ptr(gm), _ptr(grad_rgb),
+                                          _ptr(grad_sigma), _stream()), "mpf_warp_composite_bwd")
+    return grad_rgb, grad_sigma
+
+
 @_on_device
 def src_flow(sigma_S1HW, K_inv, depth_S, homs_tgt_src, flow_clip=200.0):
     """Stage C alone (mpf_src_flow): volume-rendered flows [P,2,H,W] of P <= 2 poses from a bare sigma tensor [S,1,H,W] | [S,H,W]."""
@@ -2066,6 +2097,22 @@ def homography_sample(src_SCHW, H_src_tgt, want_flow=True):
 
 
 @_on_device
+def homography_sample_backward(g_tgt_SCHW, H_src_tgt, c0=0, c1=None, grad_src=None):
+    """Adjoint of homography_sample with respect to src for the channels [c0, c1) (mpf_homography_sample_bwd): grad_src [S,C,H,W] += weight * g_tgt through
+    the taps the forward read.  grad_src: a zero-initialised buffer to add into (allocated zeroed when None); channels outside the range stay as they
+    are.  The adds are float atomics: their arrival order decides the last bits of each sum."""
+    lib = _lib.load()
+    g = _dev(g_tgt_SCHW, "g_tgt")
+    S, C, H, W = g.shape
+    c1 = C if c1 is None else c1
+    dparams = upload_params(host_math.pack_params(homs=host_math._cpu32(H_src_tgt).reshape(S, 3, 3)), g.device)
+    grad_src = _grad_buffer(grad_src, "grad_src", (S, C, H, W), g.device, True)
+    _lib.check(lib.mpf_homography_sample_bwd(_ptr(g), _ptr(dparams), S, C, H, W, int(c0), int(c1), _ptr(grad_src), _stream()),
+               "mpf_homography_sample_bwd")
+    return grad_src
+
+
+@_on_device
 def homography_flow(H_tgt_src, H, W, device):
     lib = _lib.load()
     hts = host_math._cpu32(H_tgt_src).reshape(-1, 3, 3)
@@ -2097,6 +2144,40 @@ def volume_render(rgb_S3N, sigma_SN, xyz_S3N, extra_SEN=None, hard=False, want_t
     _lib.check(lib.mpf_volume_render(_ptr(rgb), _ptr(sigma), _ptr(xyz), S, N, _ptr(out["rgb"]), _ptr(out["depth"]),
                                      _ptr(out["tacc"]), _ptr(out["weights"]), _ptr(extra), E, _ptr(out["extra"]),
                                      int(bool(hard)), _stream()), "mpf_volume_render")
+    return out
+
+
+@_on_device
+def volume_render_backward(rgb_S3N, sigma_SN, xyz_S3N, extra_SEN=None, hard=False, g_rgb=None, g_depth=None, g_extra=None, g_weights=None, g_tacc=None,
+                           want_rgb=True, want_extra=True):
+    """Adjoint of volume_render with respect to rgb, sigma and the extras (mpf_volume_render_bwd); xyz is constant.  The same inputs as the forward call
+    and the upstream gradient of each output that was used (None otherwise).  -> dict(rgb [S,3,*tail] | None, sigma [S,*tail], extra [S,E,*tail] | None)."""
+    lib = _lib.load()
+    xyz = _dev(xyz_S3N, "xyz")
+    S = xyz.shape[0]
+    tail = tuple(xyz.shape[2:])
+    N = xyz[0, 0].numel()
+    sigma = _dev(sigma_SN, "sigma")
+    rgb = _dev(rgb_S3N, "rgb") if rgb_S3N is not None else None
+    extra = _dev(extra_SEN, "extra") if extra_SEN is not None else None
+    E = 0 if extra is None else extra.shape[1]
+    dev = xyz.device
+
+    def up(t, name, lead):
+        if t is None:
+            return None
+        t = _dev(t, name)
+        if t.numel() != lead * N:
+            raise _lib.MpiFlowHipError("%s has %d elements, expected %d" % (name, t.numel(), lead * N))
+        return t
+
+    gr, gd, ge = up(g_rgb if rgb is not None else None, "g_rgb", 3), up(g_depth, "g_depth", 1), up(g_extra if E else None, "g_extra", E)
+    gw, ga = up(g_weights, "g_weights", S), up(g_tacc, "g_tacc", S)
+    out = dict(rgb=torch.empty((S, 3) + tail, dtype=_f32, device=dev) if (rgb is not None and want_rgb) else None,
+               sigma=torch.empty((S,) + tail, dtype=_f32, device=dev),
+               extra=torch.empty((S, E) + tail, dtype=_f32, device=dev) if (E and want_extra) else None)
+    _lib.check(lib.mpf_volume_render_bwd(_ptr(rgb), _ptr(sigma), _ptr(xyz), _ptr(extra), S, N, E, int(bool(hard)), _ptr(gr), _ptr(gd), _ptr(ge), _ptr(gw),
+                                         _ptr(ga), _ptr(out["rgb"]), _ptr(out["sigma"]), _ptr(out["extra"]), _stream()), "mpf_volume_render_bwd")
     return out
 
 

@@ -1,10 +1,13 @@
 """Drop-in for the reference's utils/mpi/homography_sampler.py: same class, same method signatures, same return
 values; the per-pixel work runs in HIP kernels (mpf_homography_sample / mpf_homography_flow), the [B,3,3] homographies
-are built on the host exactly as the reference builds them (batched torch-CPU matmuls + one fp64 inverse)."""
+are built on the host exactly as the reference builds them (batched torch-CPU matmuls + one fp64 inverse).
+
+sample() is differentiable with respect to the tensor it warps (see its docstring and _autograd.py); the homographies are constants."""
 import numpy as np
 import torch
 
 from ... import host_math, ops
+from . import _autograd
 
 
 def inverse(matrices):
@@ -60,14 +63,23 @@ class HomographySample:
         R_tnd = R - torch.matmul(t.unsqueeze(2), n.unsqueeze(1)) / -d33
         return torch.matmul(Kt, torch.matmul(R_tnd, Kinv))
 
-    def sample(self, src_BCHW, d_src_B, G_tgt_src, K_src_inv, K_tgt):
+    def sample(self, src_BCHW, d_src_B, G_tgt_src, K_src_inv, K_tgt, _grad_ranges=None):
         """Warp every plane b of src_BCHW to the target view by its plane-induced homography (:80-158).
-        :return: tgt_BCHW, valid_mask BxHxW (bool), flowB2A BxHxWx2"""
+        :return: tgt_BCHW, valid_mask BxHxW (bool), flowB2A BxHxWx2
+
+        Differentiable with respect to src_BCHW (float32, on the GPU): when it requires grad, tgt_BCHW carries a grad_fn whose backward is
+        mpf_homography_sample_bwd - float atomic adds through the forward's taps, so the gradient's last bits depend on the order of the adds.
+        valid_mask and flowB2A carry no gradient.  d_src_B, G_tgt_src, K_src_inv and K_tgt are constants: one that requires grad is refused
+        (MpiFlowHipError).  _grad_ranges (not a reference argument): the channel ranges whose gradient is wanted, all by default."""
         assert src_BCHW.size(2) == self.Height_tgt and src_BCHW.size(3) == self.Width_tgt, \
             "the HIP sampler renders at the source resolution (as every caller in the reference does)"
+        _autograd.refuse_geometry("HomographySample.sample", d_src_B=d_src_B, G_tgt_src=G_tgt_src, K_src_inv=K_src_inv, K_tgt=K_tgt)
         H_tgt_src = self._homographies(d_src_B, G_tgt_src, K_src_inv, K_tgt)
         with torch.no_grad():
             H_src_tgt = inverse(H_tgt_src.to(torch.float64)).to(torch.float32)
+        if _autograd.wants_grad(src_BCHW):
+            _autograd.check_values("HomographySample.sample", src_BCHW=src_BCHW)
+            return _autograd.HomographySampleFn.apply(src_BCHW, H_src_tgt, _grad_ranges)
         tgt, valid, flow = ops.homography_sample(src_BCHW, H_src_tgt)
         return tgt.to(src_BCHW.dtype), valid, flow
 

@@ -9,10 +9,18 @@ mpiflow_amd.pipeline / utils.utils.render_3dphoto_dynamic.
 Also provided although MPI-Flow's generation never takes them: alpha_composition / use_alpha=True (:42-59) and
 get_xyz_from_depth (:157-177).  Not provided: disparity_consistency_src_to_tgt (:180-210), a training loss of the MINE code
 base this module was taken from.
+
+Differentiable (HIP backward kernels, mpf_render_bwd.hip, behind the Functions of _autograd.py): plane_volume_rendering,
+plane_volume_rendering_flow, render and render_tgt_rgb_depth, with respect to the plane colours, densities and extra values (rgb_BS3HW, sigma_BS1HW,
+src_sigma_BS1HW, src_flow_BS2HW, obj_mask, mpi_rgb_src, mpi_sigma_src).  Geometry - every xyz tensor, mpi_disparity_src, G_tgt_src, K_src_inv,
+K_tgt - is constant: one that requires grad while grad mode is on raises MpiFlowHipError naming it; so do is_bg_depth_inf=True with gradients,
+tensors that are not float32 on one GPU, and double backward.  With no input requiring grad, or under torch.no_grad(), every function takes the
+path it took before.  Forward only: alpha_composition, weighted_sum_mpi, the get_*_xyz_* helpers.
 """
 import torch
 
-from ... import host_math, ops
+from ... import _lib, host_math, ops
+from . import _autograd
 from .homography_sampler import HomographySample
 from .rendering_utils import transform_G_xyz  # noqa: F401  (re-exported like the reference module does)
 
@@ -86,6 +94,14 @@ def plane_volume_rendering(rgb_BS3HW, sigma_BS1HW, xyz_BS3HW, src_sigma_BS1HW, s
     """reference :62-99 -> (rgb_out Bx3xHxW, depth_out Bx1xHxW, transparency_acc BxSx1xHxW, weights BxSx1xHxW,
     flow_out Bx2xHxW | None, obj_mask Bx1xHxW | as passed)"""
     B, S, _, H, W = sigma_BS1HW.size()
+    _autograd.refuse_geometry("plane_volume_rendering", xyz_BS3HW=xyz_BS3HW, src_xyz_BS3HW=src_xyz_BS3HW)
+    with_extra = src_sigma_BS1HW is not None
+    grad = _autograd.wants_grad(rgb_BS3HW, sigma_BS1HW, src_flow_BS2HW if with_extra else None, obj_mask if with_extra else None)
+    if grad:
+        _autograd.refuse_bg_depth_inf("plane_volume_rendering", is_bg_depth_inf)
+        _autograd.check_values("plane_volume_rendering", rgb_BS3HW=rgb_BS3HW, sigma_BS1HW=sigma_BS1HW, xyz_BS3HW=xyz_BS3HW,
+                               src_flow_BS2HW=src_flow_BS2HW if with_extra else None, obj_mask=obj_mask if with_extra else None)
+    volume_render = _autograd.volume_render if grad else ops.volume_render
     rgbs, depths, taccs, wts, flows, oms = [], [], [], [], [], []
     for b in range(B):
         extra = None
@@ -94,7 +110,7 @@ def plane_volume_rendering(rgb_BS3HW, sigma_BS1HW, xyz_BS3HW, src_sigma_BS1HW, s
             if obj_mask is not None:
                 parts.append(obj_mask[b].to(torch.float32))
             extra = torch.cat(parts, dim=1).contiguous()
-        r = ops.volume_render(rgb_BS3HW[b], sigma_BS1HW[b, :, 0], xyz_BS3HW[b], extra_SEN=extra)
+        r = volume_render(rgb_BS3HW[b], sigma_BS1HW[b, :, 0], xyz_BS3HW[b], extra_SEN=extra)
         depth = r["depth"]
         if is_bg_depth_inf:      # :146-149 (DTU option): sum(w z) + (1 - sum w) * 1000 instead of the normalised depth
             wsum = ops.weighted_sum(r["weights"])[0]
@@ -113,10 +129,17 @@ def plane_volume_rendering(rgb_BS3HW, sigma_BS1HW, xyz_BS3HW, src_sigma_BS1HW, s
 def plane_volume_rendering_flow(src_sigma_BS1HW, src_flow_BS2HW, src_xyz_BS3HW, is_bg_depth_inf, hard_flow=False):
     """reference :102-139 -> flow_out Bx2xHxW (hard_flow: the arg-max-weight plane's flow)"""
     B = src_sigma_BS1HW.size(0)
+    _autograd.refuse_geometry("plane_volume_rendering_flow", src_xyz_BS3HW=src_xyz_BS3HW)
+    grad = _autograd.wants_grad(src_sigma_BS1HW, src_flow_BS2HW)
+    if grad:
+        _autograd.refuse_bg_depth_inf("plane_volume_rendering_flow", is_bg_depth_inf)
+        _autograd.check_values("plane_volume_rendering_flow", src_sigma_BS1HW=src_sigma_BS1HW, src_flow_BS2HW=src_flow_BS2HW,
+                               src_xyz_BS3HW=src_xyz_BS3HW)
+    volume_render = _autograd.volume_render if grad else ops.volume_render
     out = []
     for b in range(B):
-        r = ops.volume_render(None, src_sigma_BS1HW[b, :, 0], src_xyz_BS3HW[b], extra_SEN=src_flow_BS2HW[b], hard=hard_flow,
-                              want_tacc=False, want_weights=False)
+        r = volume_render(None, src_sigma_BS1HW[b, :, 0], src_xyz_BS3HW[b], extra_SEN=src_flow_BS2HW[b], hard=hard_flow,
+                          want_tacc=False, want_weights=False)
         out.append(r["extra"])
     return torch.stack(out)
 
@@ -200,6 +223,21 @@ def _render_tgt_fused(mpi_rgb_src, mpi_sigma_src, mpi_disparity_src, G_tgt_src, 
     return torch.stack(rgbs), torch.stack(depths), torch.stack(tms), torch.stack(flows), (torch.stack(oms) if oms else None)
 
 
+def _render_tgt_fused_grad(mpi_rgb_src, mpi_sigma_src, mpi_disparity_src, G_tgt_src, K_src_inv, K_tgt, obj_mask):
+    """_render_tgt_fused when mpi_rgb_src or mpi_sigma_src requires grad: the same launches (same values, bit for bit), with rgb, depth and the rendered
+    mask connected to the two stacks through mpf_warp_composite_bwd.  flowA2B is computed as in _render_tgt_fused, from the detached sigma: it is
+    returned with requires_grad == False (its gradient needs fused=False).  tgt_mask never carries gradient."""
+    B = mpi_rgb_src.size(0)
+    rgb, depth, tgt_mask, om = _autograd.WarpCompositeFn.apply(mpi_rgb_src, mpi_sigma_src, mpi_disparity_src, G_tgt_src, K_src_inv, K_tgt, obj_mask)
+    flows = []
+    with torch.no_grad():
+        for b in range(B):
+            d = host_math.plane_depths(mpi_disparity_src[b])
+            H_ts, _ = host_math.homographies(G_tgt_src[b], K_src_inv[b], K_tgt[b], d)
+            flows.append(ops.src_flow(mpi_sigma_src[b].to(torch.float32), K_src_inv[b], d, H_ts.unsqueeze(0), flow_clip=0.0)[0])
+    return rgb, depth, tgt_mask, torch.stack(flows), om
+
+
 def render_tgt_rgb_depth(H_sampler: HomographySample, mpi_rgb_src, mpi_sigma_src, mpi_disparity_src, xyz_tgt_BS3HW,
                          xyz_src_BS3HW, G_tgt_src, K_src_inv, K_tgt, mpi_flow_src=None, use_alpha=False,
                          is_bg_depth_inf=False, hard_flow=False, obj_mask=None, fused=None):
@@ -210,13 +248,35 @@ def render_tgt_rgb_depth(H_sampler: HomographySample, mpi_rgb_src, mpi_sigma_src
     utils/utils.py:291-349 -, else the generic kernels that work on the materialised tensors; False = always generic; True = fused, raising
     if it does not apply.  The two forms differ by fp32 rounding only (the generic one interpolates the xyz_tgt channels bilinearly, the fused
     one evaluates the same affine field at the interpolated coordinate): both sit inside the parity bars against the reference's outputs
-    (tests/test_dropin_api.py), tgt_mask is identical."""
+    (tests/test_dropin_api.py), tgt_mask is identical.
+
+    Gradients: when mpi_rgb_src, mpi_sigma_src or obj_mask requires grad (float32, one GPU) the outputs carry them.  The generic form is then the
+    differentiable sampler followed by the differentiable render(), with torch's own cat / slice / where in between: every output but tgt_mask is
+    connected.  The fused form (taken with fused=None exactly when it would be taken without gradients, unless obj_mask itself requires grad) runs
+    mpf_warp_composite_bwd, which holds no S-deep intermediate: rgb, depth and the rendered mask get gradients to mpi_rgb_src and mpi_sigma_src;
+    flowA2B is returned with requires_grad == False - pass fused=False for its gradient.  Disparities, xyz tensors, pose and intrinsics are
+    constants (one that requires grad is refused), is_bg_depth_inf=True is refused, and both sampling adjoints add with float atomics, so the last
+    bits of a gradient depend on the order of the adds."""
+    _autograd.refuse_geometry("render_tgt_rgb_depth", mpi_disparity_src=mpi_disparity_src, xyz_tgt_BS3HW=xyz_tgt_BS3HW, xyz_src_BS3HW=xyz_src_BS3HW,
+                              G_tgt_src=G_tgt_src, K_src_inv=K_src_inv, K_tgt=K_tgt)
+    grad = _autograd.wants_grad(mpi_rgb_src, mpi_sigma_src, obj_mask)
+    if grad:
+        _autograd.refuse_bg_depth_inf("render_tgt_rgb_depth", is_bg_depth_inf)
+        _autograd.check_values("render_tgt_rgb_depth", mpi_rgb_src=mpi_rgb_src, mpi_sigma_src=mpi_sigma_src, xyz_tgt_BS3HW=xyz_tgt_BS3HW,
+                               xyz_src_BS3HW=xyz_src_BS3HW, obj_mask=obj_mask if _autograd.wants_grad(obj_mask) else None)
     if fused is None or fused:
         ok = fused_render_applies(mpi_disparity_src, xyz_tgt_BS3HW, xyz_src_BS3HW, G_tgt_src, K_src_inv, K_tgt, use_alpha, is_bg_depth_inf,
                                   hard_flow, obj_mask)
         if fused and not ok:
             raise ValueError("render_tgt_rgb_depth(fused=True): the fused kernels need default options, one mask on every plane and xyz tensors built by "
                              "this module's get_src_xyz_from_plane_disparity / get_tgt_xyz_from_plane_disparity for the same K, disparities and pose")
+        if ok and _autograd.wants_grad(obj_mask):      # the fused backward treats the mask as a constant: its gradient needs the generic form
+            if fused:
+                raise _lib.MpiFlowHipError("render_tgt_rgb_depth(fused=True): obj_mask requires grad, and the fused backward gives gradients to mpi_rgb_src "
+                                           "and mpi_sigma_src only; pass fused=False (or None) for the gradient of obj_mask")
+            ok = False
+        if ok and grad:
+            return _render_tgt_fused_grad(mpi_rgb_src, mpi_sigma_src, mpi_disparity_src, G_tgt_src, K_src_inv, K_tgt, obj_mask)
         if ok:
             return _render_tgt_fused(mpi_rgb_src, mpi_sigma_src, mpi_disparity_src, G_tgt_src, K_src_inv, K_tgt, obj_mask)
     B, S, _, H, W = mpi_rgb_src.size()
@@ -227,11 +287,14 @@ def render_tgt_rgb_depth(H_sampler: HomographySample, mpi_rgb_src, mpi_sigma_src
     G_Bs44 = G_tgt_src.unsqueeze(1).repeat(1, S, 1, 1).contiguous().reshape(B * S, 4, 4)
     Kinv_Bs33 = K_src_inv.unsqueeze(1).repeat(1, S, 1, 1).contiguous().reshape(B * S, 3, 3)
     Kt_Bs33 = K_tgt.unsqueeze(1).repeat(1, S, 1, 1).contiguous().reshape(B * S, 3, 3)
-    tgt, tgt_mask_BsHW, _ = H_sampler.sample(mpi_xyz_src.view(B * S, -1, H, W), mpi_depth_src.view(B * S), G_Bs44, Kinv_Bs33, Kt_Bs33)
+    # channels 4..6 are xyz_tgt, a constant: under autograd only the colour / density channels (and the mask's) get the sampler's scatter
+    grad_ranges = [(0, 4)] + ([(7, mpi_xyz_src.size(2))] if obj_mask is not None else [])
+    tgt, tgt_mask_BsHW, _ = H_sampler.sample(mpi_xyz_src.view(B * S, -1, H, W), mpi_depth_src.view(B * S), G_Bs44, Kinv_Bs33, Kt_Bs33,
+                                             _grad_ranges=grad_ranges)
     flowB2A = H_sampler.sample_inverse(mpi_xyz_src.view(B * S, -1, H, W), mpi_depth_src.view(B * S), G_Bs44, Kinv_Bs33, Kt_Bs33)
     flowB2A = flowB2A.permute(0, 3, 1, 2).reshape(B, S, 2, H, W)                                     # :316
     tgt = tgt.view(B, S, -1, H, W)
-    tgt_rgb, tgt_sigma, tgt_xyz = tgt[:, :, 0:3], tgt[:, :, 3:4], tgt[:, :, 4:7]
+    tgt_rgb, tgt_sigma, tgt_xyz = tgt[:, :, 0:3], tgt[:, :, 3:4], tgt[:, :, 4:7].detach()          # the sampled xyz_tgt is geometry: a constant
     tgt_om = tgt[:, :, 7:] if obj_mask is not None else None
     tgt_sigma = torch.where(tgt_xyz[:, :, -1:] >= 0, tgt_sigma, torch.zeros_like(tgt_sigma))        # :336-338
     rgb_syn, depth_syn, _, _, flowA2B, om_sync = render(tgt_rgb.contiguous(), tgt_sigma.contiguous(), tgt_xyz.contiguous(),
