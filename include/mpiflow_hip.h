@@ -143,6 +143,13 @@ int mpf_warp_composite_split(const float *d_rgb_S3HW, const float *d_sigma_SHW, 
 int mpf_warp_composite_bwd(const float *d_rgb_S3HW, const float *d_sigma_SHW, const float *d_mask_quads, const float *d_params, int S, int H, int W,
                            const float *d_g_rgb, const float *d_g_depth, const float *d_g_objmask, float *d_grad_rgb_S3HW, float *d_grad_sigma_SHW,
                            void *stream);
+/* mpf_warp_composite_bwd plus the gradient of the S plane disparities (d_grad_disparity [S]; NULL together with d_partial: exactly
+ * mpf_warp_composite_bwd).  Per target pixel q and plane s the scan yields dL/dxyz_tgt_s(q) as mpf_volume_render_bwd_xyz does, the analytic field gives
+ * d xyz_tgt_s(q) / d disparity_s = -depth_s (xyz_tgt_s(q) - t), and the dot product is summed over the pixels per plane without atomics (see
+ * mpf_src_xyz_bwd): d_partial [tiles, S] with tiles = ceil(W/32) * ceil(H/8), partial_blocks rows.  No [S,3,H,W] gradient is written. */
+int mpf_warp_composite_bwd_disp(const float *d_rgb_S3HW, const float *d_sigma_SHW, const float *d_mask_quads, const float *d_params, int S, int H, int W,
+                                const float *d_g_rgb, const float *d_g_depth, const float *d_g_objmask, float *d_grad_rgb_S3HW, float *d_grad_sigma_SHW,
+                                float *d_partial, int partial_blocks, float *d_grad_disparity, void *stream);
 
 /* Stage C alone on a bare sigma tensor [S,H,W]: the volume-rendered flows of P = 1 or 2 poses (HomographySample.sample_inverse,
  * utils/mpi/homography_sampler.py:160-220, + plane_volume_rendering_flow, utils/mpi/mpi_rendering.py:102-139) - what
@@ -1058,6 +1065,25 @@ int mpf_volume_render_bwd(const float *d_rgb, const float *d_sigma, const float 
  * forward read (same d_params), as float atomic adds: d_g_src must be zero-initialised (or hold a sum to add to), channels outside the range are not
  * touched, and the last bits of the result depend on the order in which the adds arrive.  valid and flowB2A have no gradient. */
 int mpf_homography_sample_bwd(const float *d_g_tgt, const float *d_params, int S, int C, int H, int W, int c0, int c1, float *d_g_src, void *stream);
+/* mpf_volume_render_bwd plus the gradient of xyz: d_grad_xyz [S,3,N] (NULL: exactly mpf_volume_render_bwd).  With dL/dt_j of that adjoint:
+ * dL/ddist_j = -sigma_j t_j dL/dt_j (j < S-1; the last distance is the constant 1e3), u_j = (xyz_{j+1} - xyz_j) / dist_j (0 where dist_j = 0, as torch's
+ * norm), dL/dxyz_s = u_{s-1} dL/ddist_{s-1} - u_s dL/ddist_s + (0, 0, 1) g_depth w_s / (D + 1e-5).  hard != 0: exactly zero.  One store per element, no
+ * atomics: two runs give the same bits. */
+int mpf_volume_render_bwd_xyz(const float *d_rgb, const float *d_sigma, const float *d_xyz, const float *d_extra_in, int S, int64_t N, int E, int hard,
+                              const float *d_g_rgb, const float *d_g_depth, const float *d_g_extra, const float *d_g_weights, const float *d_g_tacc,
+                              float *d_grad_rgb, float *d_grad_sigma, float *d_grad_extra, float *d_grad_xyz, void *stream);
+/* The per-plane sums over all pixels of the three launchers below use no atomics: wave sum -> LDS slot [wave][s] -> d_partial [blocks, S] (a workspace
+ * of the caller's, partial_blocks rows, nothing to initialise) -> a second kernel that adds the rows in order, in double.  S < 4096.
+ *
+ * Adjoint of mpf_src_xyz with respect to the plane DISPARITIES (same d_params): g_xyz [S,3,H,W] -> grad_disparity [S],
+ * dL/ddisparity_s = -depth_s^2 sum_p <g_s(p), K^-1 (x, y, 1)>.  blocks = ceil(H*W / 256). */
+int mpf_src_xyz_bwd(const float *d_g_xyz_S3HW, const float *d_params, int S, int H, int W, float *d_partial, int partial_blocks,
+                    float *d_grad_disparity, void *stream);
+/* Adjoint of mpf_homography_flow with respect to the plane DEPTH d_s of H_s = K_tgt (R + t n^T / d_s) K_src^-1, n = (0, 0, 1): g_flow [S,H,W,2] ->
+ * grad_depth [S].  d_params: mpf_homography_flow's records (H_tgt_src in [0..8]) with [9] = d_s, [10..12] = K_tgt t and [13..15] = the third row of
+ * K_src^-1; d(X, Y, Z)/dd = -(K_tgt t) <row, (x, y, 1)> / d^2 and the flow's derivative follows by the quotient rule.  blocks = ceil(H*W / 256). */
+int mpf_plane_flow_bwd(const float *d_g_flow_SHW2, const float *d_params, int S, int H, int W, float *d_partial, int partial_blocks, float *d_grad_depth,
+                       void *stream);
 
 /* weighted_sum_mpi's sums with caller-supplied weights (utils/mpi/mpi_rendering.py:143-152):
  * out[c,n] = cascade-sum_s weights[s,n] * values[s,c,n]   (values NULL: plain sum of the weights, C must be 1) */

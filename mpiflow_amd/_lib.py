@@ -352,6 +352,10 @@ SIGNATURES = {
     "mpf_volume_render_bwd": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i64, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "mpf_homography_sample_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
     "mpf_warp_composite_bwd": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "mpf_volume_render_bwd_xyz": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i64, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "mpf_warp_composite_bwd_disp": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
+    "mpf_src_xyz_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p]),
+    "mpf_plane_flow_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p]),
     "mpf_weighted_sum": (c_i, [c_p, c_p, c_i, c_i, c_i64, c_p, c_p]),
     "mpf_alpha_composite": (c_i, [c_p, c_p, c_i, c_i, c_i64, c_p, c_p, c_p, c_p]),
     "mpf_disp_to_depth": (c_i, [c_p, c_i64, c_p, c_p]),

@@ -242,11 +242,15 @@ def _grad_buffer(t, name, shape, device, zero):
 
 
 @_on_device
-def warp_composite_split_backward(rgb_S3HW, sigma_S1HW, quads, dparams, g_rgb, g_depth=None, g_objmask=None, grad_rgb=None, grad_sigma=None):
+def warp_composite_split_backward(rgb_S3HW, sigma_S1HW, quads, dparams, g_rgb, g_depth=None, g_objmask=None, grad_rgb=None, grad_sigma=None,
+                                  want_disparity=False):
     """Adjoint of warp_composite_split with respect to the two stacks (mpf_warp_composite_bwd): the same rgb, sigma, quads and dparams as the forward
     call, the upstream gradients of rgb [3,H,W], depth [H,W] | None and objmask [H,W] | None.  -> (grad_rgb [S,3,H,W], grad_sigma [S,H,W]).  The kernel
     ADDS into grad_rgb / grad_sigma with float atomics: pass zero-initialised buffers (or none: they are allocated zeroed).  The order in which the adds
-    arrive decides the last bits of each sum, so two runs may differ there."""
+    arrive decides the last bits of each sum, so two runs may differ there.
+
+    want_disparity: -> (grad_rgb, grad_sigma, grad_disparity [S]) through mpf_warp_composite_bwd_disp; the [tiles, S] workspace of its per-plane sums is
+    allocated here.  That gradient uses no atomics: two runs give the same bits."""
     lib = _lib.load()
     rgb_in = _dev(rgb_S3HW, "rgb stack")
     S, C, H, W = rgb_in.shape
@@ -258,6 +262,13 @@ def warp_composite_split_backward(rgb_S3HW, sigma_S1HW, quads, dparams, g_rgb, g
     gm = _dev(g_objmask, "g_objmask").reshape(H, W) if g_objmask is not None else None
     grad_rgb = _grad_buffer(grad_rgb, "grad_rgb", (S, 3, H, W), rgb_in.device, True)
     grad_sigma = _grad_buffer(grad_sigma, "grad_sigma", (S, H, W), rgb_in.device, True)
+    if want_disparity:
+        tiles = ((W + 31) // 32) * ((H + 7) // 8)
+        partial = torch.empty((tiles, S), dtype=_f32, device=rgb_in.device)
+        grad_disp = torch.empty((S,), dtype=_f32, device=rgb_in.device)
+        _lib.check(lib.mpf_warp_composite_bwd_disp(_ptr(rgb_in), _ptr(sig), _ptr(q), _ptr(dparams), S, H, W, _ptr(gr), _ptr(gd), _ptr(gm), _ptr(grad_rgb),
+                                                   _ptr(grad_sigma), _ptr(partial), tiles, _ptr(grad_disp), _stream()), "mpf_warp_composite_bwd_disp")
+        return grad_rgb, grad_sigma, grad_disp
     _lib.check(lib.mpf_warp_composite_bwd(_ptr(rgb_in), _ptr(sig), _ptr(q), _ptr(dparams), S, H, W, _ptr(gr), _ptr(gd), _ptr(gm), _ptr(grad_rgb),
                                           _ptr(grad_sigma), _stream()), "mpf_warp_composite_bwd")
     return grad_rgb, grad_sigma
@@ -2070,6 +2081,46 @@ def src_xyz(K_inv, depth_S, H, W, device):
     return out
 
 
+def _plane_sum_workspace(S, H, W, device):
+    """the [blocks, S] partial sums of the per-plane reductions (one row per 256-pixel workgroup) and the [S] result"""
+    blocks = (H * W + 255) // 256
+    return torch.empty((blocks, S), dtype=_f32, device=device), blocks, torch.empty((S,), dtype=_f32, device=device)
+
+
+@_on_device
+def src_xyz_backward(g_xyz_S3HW, K_inv, depth_S):
+    """Adjoint of src_xyz with respect to the plane disparities (mpf_src_xyz_bwd): g_xyz [S,3,H,W], the forward's K_inv and depths -> [S],
+    dL/ddisparity_s = -depth_s^2 sum_p <g_s(p), K^-1 (x, y, 1)>.  No atomics: two runs give the same bits."""
+    lib = _lib.load()
+    g = _dev(g_xyz_S3HW, "g_xyz")
+    S, C, H, W = g.shape
+    assert C == 3
+    d = host_math._cpu32(depth_S).reshape(-1)
+    assert d.numel() == S
+    dparams = upload_params(host_math.pack_params(K_inv=K_inv, depths=d), g.device)
+    partial, blocks, out = _plane_sum_workspace(S, H, W, g.device)
+    _lib.check(lib.mpf_src_xyz_bwd(_ptr(g), _ptr(dparams), S, H, W, _ptr(partial), blocks, _ptr(out), _stream()), "mpf_src_xyz_bwd")
+    return out
+
+
+@_on_device
+def plane_flow_backward(g_flow_SHW2, H_tgt_src, depth_S, Kt_t_S3, Kinv_row3_S3):
+    """Adjoint of homography_flow with respect to the plane depths d_s of H_s = K_tgt (R + t n^T / d_s) K_src^-1 (mpf_plane_flow_bwd): g_flow [S,H,W,2], the
+    forward's H_tgt_src [S,3,3], the depths [S], K_tgt t [S,3] and the third row of K_src^-1 [S,3] -> [S].  No atomics: two runs give the same bits."""
+    lib = _lib.load()
+    g = _dev(g_flow_SHW2, "g_flow")
+    S, H, W, two = g.shape
+    assert two == 2
+    buf = host_math.pack_params(homs=host_math._cpu32(H_tgt_src).reshape(S, 3, 3), depths=host_math._cpu32(depth_S).reshape(S))
+    rec = buf[host_math.PARAMS_HEADER:].view(-1, host_math.PLANE_RECORD)
+    rec[:S, 10:13] = host_math._cpu32(Kt_t_S3).reshape(S, 3)
+    rec[:S, 13:16] = host_math._cpu32(Kinv_row3_S3).reshape(S, 3)
+    dparams = upload_params(buf, g.device)
+    partial, blocks, out = _plane_sum_workspace(S, H, W, g.device)
+    _lib.check(lib.mpf_plane_flow_bwd(_ptr(g), _ptr(dparams), S, H, W, _ptr(partial), blocks, _ptr(out), _stream()), "mpf_plane_flow_bwd")
+    return out
+
+
 @_on_device
 def transform_xyz(G, xyz_S3N):
     lib = _lib.load()
@@ -2149,9 +2200,10 @@ def volume_render(rgb_S3N, sigma_SN, xyz_S3N, extra_SEN=None, hard=False, want_t
 
 @_on_device
 def volume_render_backward(rgb_S3N, sigma_SN, xyz_S3N, extra_SEN=None, hard=False, g_rgb=None, g_depth=None, g_extra=None, g_weights=None, g_tacc=None,
-                           want_rgb=True, want_extra=True):
-    """Adjoint of volume_render with respect to rgb, sigma and the extras (mpf_volume_render_bwd); xyz is constant.  The same inputs as the forward call
-    and the upstream gradient of each output that was used (None otherwise).  -> dict(rgb [S,3,*tail] | None, sigma [S,*tail], extra [S,E,*tail] | None)."""
+                           want_rgb=True, want_extra=True, want_xyz=False):
+    """Adjoint of volume_render with respect to rgb, sigma and the extras (mpf_volume_render_bwd) and, with want_xyz, with respect to xyz
+    (mpf_volume_render_bwd_xyz).  The same inputs as the forward call and the upstream gradient of each output that was used (None otherwise).
+    -> dict(rgb [S,3,*tail] | None, sigma [S,*tail], extra [S,E,*tail] | None, xyz [S,3,*tail] | None)."""
     lib = _lib.load()
     xyz = _dev(xyz_S3N, "xyz")
     S = xyz.shape[0]
@@ -2175,7 +2227,13 @@ def volume_render_backward(rgb_S3N, sigma_SN, xyz_S3N, extra_SEN=None, hard=Fals
     gw, ga = up(g_weights, "g_weights", S), up(g_tacc, "g_tacc", S)
     out = dict(rgb=torch.empty((S, 3) + tail, dtype=_f32, device=dev) if (rgb is not None and want_rgb) else None,
                sigma=torch.empty((S,) + tail, dtype=_f32, device=dev),
-               extra=torch.empty((S, E) + tail, dtype=_f32, device=dev) if (E and want_extra) else None)
+               extra=torch.empty((S, E) + tail, dtype=_f32, device=dev) if (E and want_extra) else None,
+               xyz=torch.empty((S, 3) + tail, dtype=_f32, device=dev) if want_xyz else None)
+    if want_xyz:
+        _lib.check(lib.mpf_volume_render_bwd_xyz(_ptr(rgb), _ptr(sigma), _ptr(xyz), _ptr(extra), S, N, E, int(bool(hard)), _ptr(gr), _ptr(gd), _ptr(ge),
+                                                 _ptr(gw), _ptr(ga), _ptr(out["rgb"]), _ptr(out["sigma"]), _ptr(out["extra"]), _ptr(out["xyz"]), _stream()),
+                   "mpf_volume_render_bwd_xyz")
+        return out
     _lib.check(lib.mpf_volume_render_bwd(_ptr(rgb), _ptr(sigma), _ptr(xyz), _ptr(extra), S, N, E, int(bool(hard)), _ptr(gr), _ptr(gd), _ptr(ge), _ptr(gw),
                                          _ptr(ga), _ptr(out["rgb"]), _ptr(out["sigma"]), _ptr(out["extra"]), _stream()), "mpf_volume_render_bwd")
     return out

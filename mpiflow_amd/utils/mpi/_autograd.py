@@ -1,14 +1,23 @@
-"""Autograd for the utils/mpi renderer: three torch.autograd.Functions over the HIP backward kernels (mpf_render_bwd.hip).
+"""Autograd for the utils/mpi renderer: torch.autograd.Functions over the HIP backward kernels (mpf_render_bwd.hip).
 
-Gradients flow to the per-plane VALUES only - colour, density, the "extra" channels (flow, object mask) and the sampler's source tensor.  Geometry is
-constant: an xyz tensor, a disparity, a pose or an intrinsic matrix that requires grad while grad mode is on is refused with MpiFlowHipError naming the
-argument (refuse_geometry), and so are is_bg_depth_inf=True, anything but float32 on one GPU (check_values) and double backward (once_differentiable).
+By default gradients flow to the per-plane VALUES only - colour, density, the "extra" channels (flow, object mask) and the sampler's source tensor.
+Geometry is constant: an xyz tensor, a disparity, a pose or an intrinsic matrix that requires grad while grad mode is on is refused with
+MpiFlowHipError naming the argument (refuse_geometry), and so are is_bg_depth_inf=True, anything but float32 on one GPU (check_values) and double
+backward (once_differentiable).
+
+plane_geometry_grad() opts in to the gradients of the geometry a plane disparity reaches: the xyz tensors (VolumeRenderFn's xyz input, the sampler's
+channels 4..6), the disparities (SrcXyzFn, and WarpCompositeFn's disparity_leaf in the fused form), xyz_src of the target transform (TransformXyzFn)
+and sample_inverse's d_src_B (PlaneFlowFn).  Poses and intrinsics stay refused.  The per-plane sums of these adjoints use no atomics and are
+reproducible from run to run.
 
 mpi_rendering.py / homography_sampler.py come here only when wants_grad() says that an eligible input requires grad; otherwise they take the code path
 they always took.  Each Function's forward IS that path - the same ops calls with the same arguments - so the values are the same bits.
 
 The two sampling adjoints (homography_sample_backward, warp_composite_split_backward) scatter with float atomic adds: the order in which the adds arrive
 decides the last bits of each gradient, so two runs of one backward may differ there.  A deterministic gather form is not provided."""
+import contextlib
+import threading
+
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -21,14 +30,45 @@ def wants_grad(*tensors):
     return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
 
 
-def refuse_geometry(who, **named):
-    """Geometry is constant here: raise if grad mode is on and one of the named tensors requires grad."""
+_state = threading.local()
+
+
+@contextlib.contextmanager
+def plane_geometry_grad():
+    """Opt in to the gradients of the plane geometry: inside this context (re-entrant, per thread) the xyz tensors, mpi_disparity_src and sample_inverse's
+    d_src_B may require grad and receive the reference's gradient; poses and intrinsics stay constants.  The flag is read when a function is CALLED: a
+    graph built inside the context can be differentiated after leaving it."""
+    depth = getattr(_state, "depth", 0)
+    _state.depth = depth + 1
+    try:
+        yield
+    finally:
+        _state.depth = depth
+
+
+def geometry_grad_enabled():
+    return getattr(_state, "depth", 0) > 0
+
+
+def refuse_geometry(who, _differentiable=(), **named):
+    """Geometry is constant here: raise if grad mode is on and one of the named tensors requires grad.  Inside plane_geometry_grad() the names listed in
+    _differentiable pass; poses and intrinsics are never listed."""
     if not torch.is_grad_enabled():
         return
+    on = geometry_grad_enabled()
     for name, t in named.items():
-        if isinstance(t, torch.Tensor) and t.requires_grad:
+        if isinstance(t, torch.Tensor) and t.requires_grad and not (on and name in _differentiable):
+            if on:
+                raise _lib.MpiFlowHipError("%s: %s requires grad, but poses and intrinsics stay constant inside plane_geometry_grad() too (it opens the xyz "
+                                           "tensors, the plane disparities and sample_inverse's d_src_B only); detach %s" % (who, name, name))
             raise _lib.MpiFlowHipError("%s: %s requires grad, but the HIP renderer is differentiable with respect to the plane colours, densities and extra "
-                                       "values only - geometry (xyz, disparities, poses, intrinsics) is constant; detach %s" % (who, name, name))
+                                       "values only - geometry (xyz, disparities, poses, intrinsics) is constant; detach %s (xyz tensors and disparities "
+                                       "get gradients inside mpiflow_amd.utils.mpi.plane_geometry_grad())" % (who, name, name))
+
+
+def wants_geometry_grad(*tensors):
+    """wants_grad, inside plane_geometry_grad() only"""
+    return geometry_grad_enabled() and wants_grad(*tensors)
 
 
 def check_values(who, **named):
@@ -72,8 +112,8 @@ class HomographySampleFn(Function):
 
 
 class VolumeRenderFn(Function):
-    """ops.volume_render for one batch item with the gradients of rgb, sigma and the extras; all five outputs are connected.
-    -> (rgb | None, depth, tacc | None, weights | None, extra | None)"""
+    """ops.volume_render for one batch item with the gradients of rgb, sigma and the extras - and of xyz when it requires grad (the callers let it only
+    inside plane_geometry_grad()); all five outputs are connected.  -> (rgb | None, depth, tacc | None, weights | None, extra | None)"""
 
     @staticmethod
     def forward(ctx, rgb_S3N, sigma_SN, xyz_S3N, extra_SEN, hard, want_tacc, want_weights):
@@ -91,8 +131,9 @@ class VolumeRenderFn(Function):
             g_depth = g_tacc = g_weights = None
         g = ops.volume_render_backward(rgb, sigma, xyz, extra, hard=ctx.hard, g_rgb=g_rgb, g_depth=g_depth, g_extra=g_extra, g_weights=g_weights,
                                        g_tacc=g_tacc, want_rgb=rgb is not None and ctx.needs_input_grad[0],
-                                       want_extra=extra is not None and ctx.needs_input_grad[3])
-        return (g["rgb"].reshape(rgb.shape) if g["rgb"] is not None else None, g["sigma"].reshape(sigma.shape), None,
+                                       want_extra=extra is not None and ctx.needs_input_grad[3], want_xyz=ctx.needs_input_grad[2])
+        return (g["rgb"].reshape(rgb.shape) if g["rgb"] is not None else None, g["sigma"].reshape(sigma.shape),
+                g["xyz"].reshape(xyz.shape) if g["xyz"] is not None else None,
                 g["extra"].reshape(extra.shape) if g["extra"] is not None else None, None, None, None)
 
 
@@ -105,10 +146,12 @@ def volume_render(rgb_S3N, sigma_SN, xyz_S3N, extra_SEN=None, hard=False, want_t
 class WarpCompositeFn(Function):
     """The fused standard call of render_tgt_rgb_depth (mpf_warp_composite_split per batch item) with the gradients of the rgb and sigma stacks
     (mpf_warp_composite_bwd): no [S,C,H,W] intermediate in either direction.  obj_mask is a constant here; tgt_mask carries no gradient.
+    disparity_leaf (BxS | None): the disparity tensor the xyz tensors were built from, when it requires grad inside plane_geometry_grad() - it receives the
+    gradient that the reference sends through xyz_tgt (mpf_warp_composite_bwd_disp); mpi_disparity_src itself only feeds the constant homographies.
     -> (rgb Bx3xHxW, depth Bx1xHxW, tgt_mask Bx1xHxW, objmask Bx1xHxW | None)"""
 
     @staticmethod
-    def forward(ctx, mpi_rgb_src, mpi_sigma_src, mpi_disparity_src, G_tgt_src, K_src_inv, K_tgt, obj_mask):
+    def forward(ctx, mpi_rgb_src, mpi_sigma_src, mpi_disparity_src, G_tgt_src, K_src_inv, K_tgt, obj_mask, disparity_leaf=None):
         B, S, _, H, W = mpi_rgb_src.size()
         dev = mpi_rgb_src.device
         rgbs, depths, tms, oms, ctx.quads, ctx.dparams = [], [], [], [], [], []
@@ -137,9 +180,68 @@ class WarpCompositeFn(Function):
         grad_sigma = torch.zeros_like(mpi_sigma_src, memory_format=torch.contiguous_format)
         if g_rgb is None:
             g_rgb = torch.zeros((B, 3, H, W), dtype=torch.float32, device=mpi_rgb_src.device)
+        want_disp = len(ctx.needs_input_grad) > 7 and ctx.needs_input_grad[7]
+        grad_disp = []
         for b in range(B):
-            ops.warp_composite_split_backward(mpi_rgb_src[b], mpi_sigma_src[b], ctx.quads[b], ctx.dparams[b], g_rgb[b],
-                                              g_depth[b] if g_depth is not None else None,
-                                              g_om[b] if (g_om is not None and ctx.quads[b] is not None) else None,
-                                              grad_rgb=grad_rgb[b], grad_sigma=grad_sigma[b].view(S, H, W))
-        return grad_rgb, grad_sigma, None, None, None, None, None
+            more = dict(want_disparity=True) if want_disp else {}
+            r = ops.warp_composite_split_backward(mpi_rgb_src[b], mpi_sigma_src[b], ctx.quads[b], ctx.dparams[b], g_rgb[b],
+                                                  g_depth[b] if g_depth is not None else None,
+                                                  g_om[b] if (g_om is not None and ctx.quads[b] is not None) else None,
+                                                  grad_rgb=grad_rgb[b], grad_sigma=grad_sigma[b].view(S, H, W), **more)
+            if want_disp:
+                grad_disp.append(r[2])
+        return grad_rgb, grad_sigma, None, None, None, None, None, (torch.stack(grad_disp) if want_disp else None)
+
+
+class SrcXyzFn(Function):
+    """get_src_xyz_from_plane_disparity with the gradient of the disparities (mpf_src_xyz_bwd).  forward: the launches the plain path makes."""
+
+    @staticmethod
+    def forward(ctx, mpi_disparity_src, K_src_inv, H, W):
+        B = mpi_disparity_src.size(0)
+        ctx.K_src_inv = K_src_inv
+        ctx.depths = [host_math.plane_depths(mpi_disparity_src[b]) for b in range(B)]
+        return torch.stack([ops.src_xyz(K_src_inv[b], ctx.depths[b], H, W, mpi_disparity_src.device) for b in range(B)])
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_xyz):
+        return torch.stack([ops.src_xyz_backward(g_xyz[b], ctx.K_src_inv[b], ctx.depths[b]) for b in range(g_xyz.size(0))]), None, None, None
+
+
+class TransformXyzFn(Function):
+    """get_tgt_xyz_from_plane_disparity with the gradient of xyz_src: R^T g, which is mpf_transform_xyz with the header [R^T | 0]."""
+
+    @staticmethod
+    def forward(ctx, xyz_src_BS3HW, G_tgt_src):
+        B, S, _, H, W = xyz_src_BS3HW.size()
+        ctx.G_tgt_src = G_tgt_src
+        return torch.stack([ops.transform_xyz(G_tgt_src[b], xyz_src_BS3HW[b].reshape(S, 3, H * W)).reshape(S, 3, H, W) for b in range(B)])
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        B, S, _, H, W = g.size()
+        out = []
+        for b in range(B):
+            Gt = torch.zeros(4, 4, dtype=torch.float32)
+            Gt[0:3, 0:3] = host_math._cpu32(ctx.G_tgt_src[b]).reshape(4, 4)[0:3, 0:3].t()
+            Gt[3, 3] = 1.0
+            out.append(ops.transform_xyz(Gt, g[b].reshape(S, 3, H * W)).reshape(S, 3, H, W))
+        return torch.stack(out), None
+
+
+class PlaneFlowFn(Function):
+    """HomographySample.sample_inverse with the gradient of d_src_B (mpf_plane_flow_bwd).  H_tgt_src, d_host, Kt_t and Kinv_row3 are the host's constants
+    of the forward; d_src_B only receives the gradient."""
+
+    @staticmethod
+    def forward(ctx, d_src_B, H_tgt_src, d_host, Kt_t, Kinv_row3, H, W, device):
+        ctx.consts = (H_tgt_src, d_host, Kt_t, Kinv_row3)
+        ctx.shape = d_src_B.shape
+        return ops.homography_flow(H_tgt_src, H, W, device)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_flow):
+        return (ops.plane_flow_backward(g_flow, *ctx.consts).reshape(ctx.shape),) + (None,) * 7

@@ -2,7 +2,10 @@
 values; the per-pixel work runs in HIP kernels (mpf_homography_sample / mpf_homography_flow), the [B,3,3] homographies
 are built on the host exactly as the reference builds them (batched torch-CPU matmuls + one fp64 inverse).
 
-sample() is differentiable with respect to the tensor it warps (see its docstring and _autograd.py); the homographies are constants."""
+sample() is differentiable with respect to the tensor it warps (see its docstring and _autograd.py); the homographies are constants.  Inside
+mpiflow_amd.utils.mpi.plane_geometry_grad() sample_inverse() is differentiable with respect to d_src_B (mpf_plane_flow_bwd), and sample() accepts a
+d_src_B that requires grad without giving it a gradient - the reference inverts the homography under torch.no_grad(), so its sampling grid gives none
+either.  Poses and intrinsics stay constants."""
 import numpy as np
 import torch
 
@@ -70,10 +73,13 @@ class HomographySample:
         Differentiable with respect to src_BCHW (float32, on the GPU): when it requires grad, tgt_BCHW carries a grad_fn whose backward is
         mpf_homography_sample_bwd - float atomic adds through the forward's taps, so the gradient's last bits depend on the order of the adds.
         valid_mask and flowB2A carry no gradient.  d_src_B, G_tgt_src, K_src_inv and K_tgt are constants: one that requires grad is refused
-        (MpiFlowHipError).  _grad_ranges (not a reference argument): the channel ranges whose gradient is wanted, all by default."""
+        (MpiFlowHipError).  _grad_ranges (not a reference argument): the channel ranges whose gradient is wanted, all by default.
+
+        Inside plane_geometry_grad() a d_src_B that requires grad is accepted and receives NO gradient, exactly as in the reference: there d_src_B
+        reaches the output through H_src_tgt alone, which is computed under torch.no_grad() (:121-122)."""
         assert src_BCHW.size(2) == self.Height_tgt and src_BCHW.size(3) == self.Width_tgt, \
             "the HIP sampler renders at the source resolution (as every caller in the reference does)"
-        _autograd.refuse_geometry("HomographySample.sample", d_src_B=d_src_B, G_tgt_src=G_tgt_src, K_src_inv=K_src_inv, K_tgt=K_tgt)
+        _autograd.refuse_geometry("HomographySample.sample", ("d_src_B",), d_src_B=d_src_B, G_tgt_src=G_tgt_src, K_src_inv=K_src_inv, K_tgt=K_tgt)
         H_tgt_src = self._homographies(d_src_B, G_tgt_src, K_src_inv, K_tgt)
         with torch.no_grad():
             H_src_tgt = inverse(H_tgt_src.to(torch.float64)).to(torch.float32)
@@ -83,8 +89,22 @@ class HomographySample:
         tgt, valid, flow = ops.homography_sample(src_BCHW, H_src_tgt)
         return tgt.to(src_BCHW.dtype), valid, flow
 
-    def sample_inverse(self, src_BCHW, d_src_B, G_tgt_src, K_src_inv, K_tgt):
+    def sample_inverse(self, src_BCHW, d_src_B, G_tgt_src, K_src_inv, K_tgt, _d_host=None):
         """Per-plane forward flow of every source pixel (:160-220).  src_BCHW is used for its shape/device only.
-        :return: flowA2B BxHxWx2"""
-        H_tgt_src = self._homographies(d_src_B, G_tgt_src, K_src_inv, K_tgt)
+        :return: flowA2B BxHxWx2
+
+        Inside plane_geometry_grad() a d_src_B that requires grad (float32, on the GPU) receives the flow's gradient (mpf_plane_flow_bwd): with
+        H = A + B / d, A = K_tgt R K_src^-1, B = K_tgt t n^T K_src^-1 and (X, Y, Z) = H (x, y, 1), d(X, Y, Z)/dd = -B (x, y, 1) / d^2 and
+        d flow / dd follows by the quotient rule.  Outside it the flow carries no grad_fn, as before; inside it G_tgt_src, K_src_inv and K_tgt are refused when they require grad.
+        _d_host (not a reference argument): the host copy of d_src_B to build the homographies from."""
+        if _autograd.geometry_grad_enabled():          # outside, the flow is returned without a grad_fn whatever requires grad, as it always was
+            _autograd.refuse_geometry("HomographySample.sample_inverse", ("d_src_B",), d_src_B=d_src_B, G_tgt_src=G_tgt_src, K_src_inv=K_src_inv,
+                                      K_tgt=K_tgt)
+        d_host = d_src_B if _d_host is None else _d_host
+        H_tgt_src = self._homographies(d_host, G_tgt_src, K_src_inv, K_tgt)
+        if _autograd.wants_geometry_grad(d_src_B):
+            _autograd.check_values("HomographySample.sample_inverse", d_src_B=d_src_B)
+            Kt_t = torch.matmul(K_tgt.detach().to("cpu", torch.float32), G_tgt_src.detach().to("cpu", torch.float32)[:, 0:3, 3:4]).squeeze(2)
+            return _autograd.PlaneFlowFn.apply(d_src_B, H_tgt_src, d_host.detach().to("cpu", torch.float32).reshape(-1), Kt_t,
+                                               K_src_inv.detach().to("cpu", torch.float32)[:, 2, :], self.Height_tgt, self.Width_tgt, src_BCHW.device)
         return ops.homography_flow(H_tgt_src, self.Height_tgt, self.Width_tgt, src_BCHW.device)

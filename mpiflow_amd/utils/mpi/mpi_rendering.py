@@ -15,7 +15,12 @@ plane_volume_rendering_flow, render and render_tgt_rgb_depth, with respect to th
 src_sigma_BS1HW, src_flow_BS2HW, obj_mask, mpi_rgb_src, mpi_sigma_src).  Geometry - every xyz tensor, mpi_disparity_src, G_tgt_src, K_src_inv,
 K_tgt - is constant: one that requires grad while grad mode is on raises MpiFlowHipError naming it; so do is_bg_depth_inf=True with gradients,
 tensors that are not float32 on one GPU, and double backward.  With no input requiring grad, or under torch.no_grad(), every function takes the
-path it took before.  Forward only: alpha_composition, weighted_sum_mpi, the get_*_xyz_* helpers.
+path it took before.  Forward only: alpha_composition, weighted_sum_mpi, get_xyz_from_depth.
+
+Inside mpiflow_amd.utils.mpi.plane_geometry_grad() the geometry that a plane disparity reaches is differentiable too:
+xyz_BS3HW, src_xyz_BS3HW, xyz_tgt_BS3HW, xyz_src_BS3HW and mpi_disparity_src (of render_tgt_rgb_depth: through sample_inverse's flow; of
+get_src_xyz_from_plane_disparity: through the xyz field), and xyz_src_BS3HW of get_tgt_xyz_from_plane_disparity.  The sampling grid gives no gradient,
+as in the reference.  G_tgt_src, K_src_inv, K_tgt, is_bg_depth_inf=True, non-float32 tensors and double backward stay refused there.
 """
 import torch
 
@@ -36,9 +41,15 @@ def _key(*small):
     return tuple(host_math._cpu32(t).contiguous().numpy().tobytes() for t in small)
 
 
-def _tag(t, what, key):
-    t._mpf_std = (what, key, t._version)
+def _tag(t, what, key, leaf=None):
+    """leaf: the disparity tensor t was built from, when it requires grad inside plane_geometry_grad() - the fused backward sends its gradient there"""
+    t._mpf_std = (what, key, t._version, leaf)
     return t
+
+
+def _tag_leaf(t):
+    tag = getattr(t, "_mpf_std", None)
+    return tag[3] if tag is not None and tag[2] == t._version else None
 
 
 def _tagged(t, what):
@@ -94,9 +105,10 @@ def plane_volume_rendering(rgb_BS3HW, sigma_BS1HW, xyz_BS3HW, src_sigma_BS1HW, s
     """reference :62-99 -> (rgb_out Bx3xHxW, depth_out Bx1xHxW, transparency_acc BxSx1xHxW, weights BxSx1xHxW,
     flow_out Bx2xHxW | None, obj_mask Bx1xHxW | as passed)"""
     B, S, _, H, W = sigma_BS1HW.size()
-    _autograd.refuse_geometry("plane_volume_rendering", xyz_BS3HW=xyz_BS3HW, src_xyz_BS3HW=src_xyz_BS3HW)
+    _autograd.refuse_geometry("plane_volume_rendering", ("xyz_BS3HW", "src_xyz_BS3HW"), xyz_BS3HW=xyz_BS3HW, src_xyz_BS3HW=src_xyz_BS3HW)
     with_extra = src_sigma_BS1HW is not None
-    grad = _autograd.wants_grad(rgb_BS3HW, sigma_BS1HW, src_flow_BS2HW if with_extra else None, obj_mask if with_extra else None)
+    grad = _autograd.wants_grad(rgb_BS3HW, sigma_BS1HW, src_flow_BS2HW if with_extra else None, obj_mask if with_extra else None) \
+        or _autograd.wants_geometry_grad(xyz_BS3HW)
     if grad:
         _autograd.refuse_bg_depth_inf("plane_volume_rendering", is_bg_depth_inf)
         _autograd.check_values("plane_volume_rendering", rgb_BS3HW=rgb_BS3HW, sigma_BS1HW=sigma_BS1HW, xyz_BS3HW=xyz_BS3HW,
@@ -129,8 +141,8 @@ def plane_volume_rendering(rgb_BS3HW, sigma_BS1HW, xyz_BS3HW, src_sigma_BS1HW, s
 def plane_volume_rendering_flow(src_sigma_BS1HW, src_flow_BS2HW, src_xyz_BS3HW, is_bg_depth_inf, hard_flow=False):
     """reference :102-139 -> flow_out Bx2xHxW (hard_flow: the arg-max-weight plane's flow)"""
     B = src_sigma_BS1HW.size(0)
-    _autograd.refuse_geometry("plane_volume_rendering_flow", src_xyz_BS3HW=src_xyz_BS3HW)
-    grad = _autograd.wants_grad(src_sigma_BS1HW, src_flow_BS2HW)
+    _autograd.refuse_geometry("plane_volume_rendering_flow", ("src_xyz_BS3HW",), src_xyz_BS3HW=src_xyz_BS3HW)
+    grad = _autograd.wants_grad(src_sigma_BS1HW, src_flow_BS2HW) or _autograd.wants_geometry_grad(src_xyz_BS3HW)
     if grad:
         _autograd.refuse_bg_depth_inf("plane_volume_rendering_flow", is_bg_depth_inf)
         _autograd.check_values("plane_volume_rendering_flow", src_sigma_BS1HW=src_sigma_BS1HW, src_flow_BS2HW=src_flow_BS2HW,
@@ -164,19 +176,38 @@ def get_src_xyz_from_plane_disparity(meshgrid_src_homo, mpi_disparity_src, K_src
                               regenerated from pixel indices in the kernel; only H and W are read from it)
     :param mpi_disparity_src: BxS
     :param K_src_inv: Bx3x3
-    :return: BxSx3xHxW"""
+    :return: BxSx3xHxW
+
+    Inside plane_geometry_grad() a mpi_disparity_src that requires grad (float32, on the GPU) receives
+    dL/ddisparity_s = -depth_s^2 sum_p <g_s(p), K^-1 (x, y, 1)> (mpf_src_xyz_bwd), and the returned tensor's tag remembers it for the fused backward.
+    K_src_inv stays a constant."""
     B, S = mpi_disparity_src.size()
     H, W = meshgrid_src_homo.size(1), meshgrid_src_homo.size(2)
     dev = mpi_disparity_src.device if mpi_disparity_src.is_cuda else meshgrid_src_homo.device
+    if _autograd.geometry_grad_enabled():              # outside, the helper is forward only whatever requires grad, as it always was
+        _autograd.refuse_geometry("get_src_xyz_from_plane_disparity", ("mpi_disparity_src",), mpi_disparity_src=mpi_disparity_src, K_src_inv=K_src_inv)
+    if _autograd.wants_geometry_grad(mpi_disparity_src):
+        _autograd.check_values("get_src_xyz_from_plane_disparity", mpi_disparity_src=mpi_disparity_src)
+        return _tag(_autograd.SrcXyzFn.apply(mpi_disparity_src, K_src_inv, H, W), "src", _key(K_src_inv, mpi_disparity_src), mpi_disparity_src)
     out = [ops.src_xyz(K_src_inv[b], host_math.plane_depths(mpi_disparity_src[b]), H, W, dev) for b in range(B)]
     return _tag(torch.stack(out), "src", _key(K_src_inv, mpi_disparity_src))
 
 
 def get_tgt_xyz_from_plane_disparity(xyz_src_BS3HW, G_tgt_src):
-    """xyz_tgt = G . [xyz_src; 1]   (reference :242-256) -> BxSx3xHxW"""
+    """xyz_tgt = G . [xyz_src; 1]   (reference :242-256) -> BxSx3xHxW
+
+    Inside plane_geometry_grad() an xyz_src_BS3HW that requires grad (float32, on the GPU) receives R^T g (mpf_transform_xyz with [R^T | 0]); the tag of
+    the result carries on the disparity tensor that xyz_src_BS3HW's tag remembers.  G_tgt_src stays a constant."""
     B, S, _, H, W = xyz_src_BS3HW.size()
+    if _autograd.geometry_grad_enabled():
+        _autograd.refuse_geometry("get_tgt_xyz_from_plane_disparity", ("xyz_src_BS3HW",), xyz_src_BS3HW=xyz_src_BS3HW, G_tgt_src=G_tgt_src)
+    src_key = _tagged(xyz_src_BS3HW, "src")
+    if _autograd.wants_geometry_grad(xyz_src_BS3HW):
+        _autograd.check_values("get_tgt_xyz_from_plane_disparity", xyz_src_BS3HW=xyz_src_BS3HW)
+        res = _autograd.TransformXyzFn.apply(xyz_src_BS3HW, G_tgt_src)
+        return _tag(res, "tgt", src_key + _key(G_tgt_src), _tag_leaf(xyz_src_BS3HW)) if src_key is not None else res
     out = [ops.transform_xyz(G_tgt_src[b], xyz_src_BS3HW[b].reshape(S, 3, H * W)).reshape(S, 3, H, W) for b in range(B)]
-    res, src_key = torch.stack(out), _tagged(xyz_src_BS3HW, "src")
+    res = torch.stack(out)
     return _tag(res, "tgt", src_key + _key(G_tgt_src)) if src_key is not None else res
 
 
@@ -223,12 +254,14 @@ def _render_tgt_fused(mpi_rgb_src, mpi_sigma_src, mpi_disparity_src, G_tgt_src, 
     return torch.stack(rgbs), torch.stack(depths), torch.stack(tms), torch.stack(flows), (torch.stack(oms) if oms else None)
 
 
-def _render_tgt_fused_grad(mpi_rgb_src, mpi_sigma_src, mpi_disparity_src, G_tgt_src, K_src_inv, K_tgt, obj_mask):
+def _render_tgt_fused_grad(mpi_rgb_src, mpi_sigma_src, mpi_disparity_src, G_tgt_src, K_src_inv, K_tgt, obj_mask, disparity_leaf=None):
     """_render_tgt_fused when mpi_rgb_src or mpi_sigma_src requires grad: the same launches (same values, bit for bit), with rgb, depth and the rendered
     mask connected to the two stacks through mpf_warp_composite_bwd.  flowA2B is computed as in _render_tgt_fused, from the detached sigma: it is
-    returned with requires_grad == False (its gradient needs fused=False).  tgt_mask never carries gradient."""
+    returned with requires_grad == False (its gradient needs fused=False).  tgt_mask never carries gradient.  disparity_leaf: the disparity tensor
+    that the xyz tensors were built from, which receives the gradient the reference sends through xyz_tgt (mpf_warp_composite_bwd_disp)."""
     B = mpi_rgb_src.size(0)
-    rgb, depth, tgt_mask, om = _autograd.WarpCompositeFn.apply(mpi_rgb_src, mpi_sigma_src, mpi_disparity_src, G_tgt_src, K_src_inv, K_tgt, obj_mask)
+    rgb, depth, tgt_mask, om = _autograd.WarpCompositeFn.apply(mpi_rgb_src, mpi_sigma_src, mpi_disparity_src.detach(), G_tgt_src, K_src_inv, K_tgt, obj_mask,
+                                                               disparity_leaf)
     flows = []
     with torch.no_grad():
         for b in range(B):
@@ -256,14 +289,22 @@ def render_tgt_rgb_depth(H_sampler: HomographySample, mpi_rgb_src, mpi_sigma_src
     mpf_warp_composite_bwd, which holds no S-deep intermediate: rgb, depth and the rendered mask get gradients to mpi_rgb_src and mpi_sigma_src;
     flowA2B is returned with requires_grad == False - pass fused=False for its gradient.  Disparities, xyz tensors, pose and intrinsics are
     constants (one that requires grad is refused), is_bg_depth_inf=True is refused, and both sampling adjoints add with float atomics, so the last
-    bits of a gradient depend on the order of the adds."""
-    _autograd.refuse_geometry("render_tgt_rgb_depth", mpi_disparity_src=mpi_disparity_src, xyz_tgt_BS3HW=xyz_tgt_BS3HW, xyz_src_BS3HW=xyz_src_BS3HW,
-                              G_tgt_src=G_tgt_src, K_src_inv=K_src_inv, K_tgt=K_tgt)
-    grad = _autograd.wants_grad(mpi_rgb_src, mpi_sigma_src, obj_mask)
+    bits of a gradient depend on the order of the adds.
+
+    Inside plane_geometry_grad(): xyz_tgt_BS3HW, xyz_src_BS3HW and mpi_disparity_src may require grad.  Generic form: the sampled xyz_tgt stays on the
+    graph (the z >= 0 gate is a constant condition), and mpi_disparity_src reaches flowA2B through sample_inverse.  Fused form: the gradient that the
+    reference sends through xyz_tgt goes to the disparity tensor the xyz tensors were built from - which their tag remembers - through
+    mpf_warp_composite_bwd_disp, without an [S,3,H,W] gradient; flowA2B stays detached there, so its gradient to a disparity (the xyz_src path and
+    the mpi_disparity_src argument's) needs fused=False.  Poses and intrinsics stay refused."""
+    _autograd.refuse_geometry("render_tgt_rgb_depth", ("mpi_disparity_src", "xyz_tgt_BS3HW", "xyz_src_BS3HW"), mpi_disparity_src=mpi_disparity_src,
+                              xyz_tgt_BS3HW=xyz_tgt_BS3HW, xyz_src_BS3HW=xyz_src_BS3HW, G_tgt_src=G_tgt_src, K_src_inv=K_src_inv, K_tgt=K_tgt)
+    geom = _autograd.wants_geometry_grad(mpi_disparity_src, xyz_tgt_BS3HW, xyz_src_BS3HW)
+    grad = _autograd.wants_grad(mpi_rgb_src, mpi_sigma_src, obj_mask) or geom
     if grad:
         _autograd.refuse_bg_depth_inf("render_tgt_rgb_depth", is_bg_depth_inf)
         _autograd.check_values("render_tgt_rgb_depth", mpi_rgb_src=mpi_rgb_src, mpi_sigma_src=mpi_sigma_src, xyz_tgt_BS3HW=xyz_tgt_BS3HW,
-                               xyz_src_BS3HW=xyz_src_BS3HW, obj_mask=obj_mask if _autograd.wants_grad(obj_mask) else None)
+                               xyz_src_BS3HW=xyz_src_BS3HW, obj_mask=obj_mask if _autograd.wants_grad(obj_mask) else None,
+                               mpi_disparity_src=mpi_disparity_src if _autograd.wants_geometry_grad(mpi_disparity_src) else None)
     if fused is None or fused:
         ok = fused_render_applies(mpi_disparity_src, xyz_tgt_BS3HW, xyz_src_BS3HW, G_tgt_src, K_src_inv, K_tgt, use_alpha, is_bg_depth_inf,
                                   hard_flow, obj_mask)
@@ -275,26 +316,44 @@ def render_tgt_rgb_depth(H_sampler: HomographySample, mpi_rgb_src, mpi_sigma_src
                 raise _lib.MpiFlowHipError("render_tgt_rgb_depth(fused=True): obj_mask requires grad, and the fused backward gives gradients to mpi_rgb_src "
                                            "and mpi_sigma_src only; pass fused=False (or None) for the gradient of obj_mask")
             ok = False
+        leaf = None
+        if ok and _autograd.wants_geometry_grad(xyz_tgt_BS3HW):
+            # the fused kernels never read xyz_tgt: its gradient goes straight to the disparity tensor it was built from, which its tag remembers
+            leaf = _tag_leaf(xyz_tgt_BS3HW)
+            if leaf is None or not leaf.requires_grad:
+                if fused:
+                    raise _lib.MpiFlowHipError("render_tgt_rgb_depth(fused=True): xyz_tgt_BS3HW requires grad but was not built from a disparity tensor "
+                                               "that requires grad by this module's helpers inside plane_geometry_grad(); pass fused=False (or None)")
+                ok = False
         if ok and grad:
-            return _render_tgt_fused_grad(mpi_rgb_src, mpi_sigma_src, mpi_disparity_src, G_tgt_src, K_src_inv, K_tgt, obj_mask)
+            return _render_tgt_fused_grad(mpi_rgb_src, mpi_sigma_src, mpi_disparity_src, G_tgt_src, K_src_inv, K_tgt, obj_mask, leaf)
         if ok:
             return _render_tgt_fused(mpi_rgb_src, mpi_sigma_src, mpi_disparity_src, G_tgt_src, K_src_inv, K_tgt, obj_mask)
     B, S, _, H, W = mpi_rgb_src.size()
     mpi_depth_src = torch.reciprocal(mpi_disparity_src.detach().to("cpu", torch.float32))          # :284
+    # the host copy above is what the homographies are built from; with a disparity gradient the reciprocal is also taken on the graph, for sample_inverse
+    depth_graph = torch.reciprocal(mpi_disparity_src).view(B * S) if _autograd.wants_geometry_grad(mpi_disparity_src) else None
+    xyz_grad = _autograd.wants_geometry_grad(xyz_tgt_BS3HW)
     mpi_xyz_src = torch.cat((mpi_rgb_src.to(torch.float32), mpi_sigma_src.to(torch.float32), xyz_tgt_BS3HW.to(torch.float32)), dim=2)
     if obj_mask is not None:
         mpi_xyz_src = torch.cat((mpi_xyz_src, obj_mask.to(torch.float32)), dim=2)
     G_Bs44 = G_tgt_src.unsqueeze(1).repeat(1, S, 1, 1).contiguous().reshape(B * S, 4, 4)
     Kinv_Bs33 = K_src_inv.unsqueeze(1).repeat(1, S, 1, 1).contiguous().reshape(B * S, 3, 3)
     Kt_Bs33 = K_tgt.unsqueeze(1).repeat(1, S, 1, 1).contiguous().reshape(B * S, 3, 3)
-    # channels 4..6 are xyz_tgt, a constant: under autograd only the colour / density channels (and the mask's) get the sampler's scatter
-    grad_ranges = [(0, 4)] + ([(7, mpi_xyz_src.size(2))] if obj_mask is not None else [])
+    # channels 4..6 are xyz_tgt, a constant unless it requires grad inside plane_geometry_grad(): under autograd only the colour / density channels (and
+    # the mask's) get the sampler's scatter
+    grad_ranges = ([(0, mpi_xyz_src.size(2))] if xyz_grad else [(0, 4)] + ([(7, mpi_xyz_src.size(2))] if obj_mask is not None else []))
     tgt, tgt_mask_BsHW, _ = H_sampler.sample(mpi_xyz_src.view(B * S, -1, H, W), mpi_depth_src.view(B * S), G_Bs44, Kinv_Bs33, Kt_Bs33,
                                              _grad_ranges=grad_ranges)
-    flowB2A = H_sampler.sample_inverse(mpi_xyz_src.view(B * S, -1, H, W), mpi_depth_src.view(B * S), G_Bs44, Kinv_Bs33, Kt_Bs33)
+    if depth_graph is not None:
+        flowB2A = H_sampler.sample_inverse(mpi_xyz_src.view(B * S, -1, H, W), depth_graph, G_Bs44, Kinv_Bs33, Kt_Bs33, _d_host=mpi_depth_src.view(B * S))
+    else:
+        flowB2A = H_sampler.sample_inverse(mpi_xyz_src.view(B * S, -1, H, W), mpi_depth_src.view(B * S), G_Bs44, Kinv_Bs33, Kt_Bs33)
     flowB2A = flowB2A.permute(0, 3, 1, 2).reshape(B, S, 2, H, W)                                     # :316
     tgt = tgt.view(B, S, -1, H, W)
-    tgt_rgb, tgt_sigma, tgt_xyz = tgt[:, :, 0:3], tgt[:, :, 3:4], tgt[:, :, 4:7].detach()          # the sampled xyz_tgt is geometry: a constant
+    tgt_rgb, tgt_sigma, tgt_xyz = tgt[:, :, 0:3], tgt[:, :, 3:4], tgt[:, :, 4:7]
+    if not xyz_grad:
+        tgt_xyz = tgt_xyz.detach()                                                                  # the sampled xyz_tgt is geometry: a constant
     tgt_om = tgt[:, :, 7:] if obj_mask is not None else None
     tgt_sigma = torch.where(tgt_xyz[:, :, -1:] >= 0, tgt_sigma, torch.zeros_like(tgt_sigma))        # :336-338
     rgb_syn, depth_syn, _, _, flowA2B, om_sync = render(tgt_rgb.contiguous(), tgt_sigma.contiguous(), tgt_xyz.contiguous(),
