@@ -49,7 +49,8 @@ extern "C" {
                              mpf_flow_encode_kitti with MpfFlowVizArgs, and now mpf_rgbd_mesh_vertices, mpf_rasterize_grid and
                              mpf_rasterize_grid_workspace with MpfMeshVertexArgs / MpfMeshRasterArgs, and now mpf_canny and mpf_canny_workspace
                              with MpfCannyArgs and the four mpf_stage2_* calls with MpfStage2Args, and now mpf_sparse_bilateral, mpf_sparse_bilateral_workspace
-                             and mpf_sparse_bilateral_rank with MpfBilateralArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
+                             and mpf_sparse_bilateral_rank with MpfBilateralArgs, and now mpf_gather_pxpy, mpf_gather_pxpy_bwd, mpf_sample_pdf,
+                             mpf_disp_consistency, its _bwd and _workspace calls with MpfGatherPxpyArgs / MpfSamplePdfArgs / MpfDispConsistencyArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
 
 /* d_params layout (floats):
  *   [0..8]   K_src^-1 (3x3 row-major)            [9..20]  G_tgt_src rows 0..2 (3x4 row-major: R | t)
@@ -966,6 +967,81 @@ typedef struct MpfBilateralArgs {
 size_t mpf_sparse_bilateral_workspace(int dtype, int B, int h, int w);   /* 0 for a dtype or shape the call refuses */
 int mpf_sparse_bilateral_rank(int n);                                    /* k*(n) for 1 <= n <= 81, else 0; host arithmetic, no GPU */
 int mpf_sparse_bilateral(const MpfBilateralArgs *a, void *stream);
+
+/* The training-time half of the reference's utils/mpi (MINE's plane samplers and its disparity-consistency loss); INTEGRATION.md section 21 states
+ * each operation by operation (tests/mpi_training_restated.py restates them in float64).  All tensors f32 and contiguous unless said otherwise;
+ * everything is validated before anything is launched (MPF_ERR_BAD_ARGUMENT), and nothing synchronises with the host.
+ *
+ * The pixel index of a coordinate v in a frame of n: rint(v) (ties to even), clamped to [0, n - 1] as a float before the cast - NaN and -inf
+ * give 0, +inf gives n - 1; an i64 coordinate is clamped as it is.
+ *
+ * mpf_gather_pxpy       out[b,c,i] = img[b,c, index(pxpy[b,1,i], H) * W + index(pxpy[b,0,i], W)]   (rendering_utils.py:26-43)
+ * mpf_gather_pxpy_bwd   grad_img[b,c,that pixel] += grad_out[b,c,i], float atomic adds into a buffer the caller zeroed: points that share a pixel
+ *                       decide the last bits of its sum by their order.  pxpy receives no gradient (the reference indexes under no_grad).
+ * Limits: B <= 65535; B * C * H * W and B * C * N below 2^31. */
+#define MPF_PXPY_F32 0
+#define MPF_PXPY_I64 1
+typedef struct MpfGatherPxpyArgs {
+    const float *img;                /* [B,C,H,W]; read by mpf_gather_pxpy */
+    const void *pxpy;                /* [B,2,N] f32 or i64 (pxpy_dtype): row 0 is x, row 1 is y */
+    float *out;                      /* [B,C,N], written by mpf_gather_pxpy */
+    const float *grad_out;           /* [B,C,N]; read by mpf_gather_pxpy_bwd */
+    float *grad_img;                 /* [B,C,H,W], added into by mpf_gather_pxpy_bwd */
+    int pxpy_dtype;                  /* MPF_PXPY_F32 / _I64 */
+    int B, C, H, W, N;
+} MpfGatherPxpyArgs;
+int mpf_gather_pxpy(const MpfGatherPxpyArgs *a, void *stream);
+int mpf_gather_pxpy_bwd(const MpfGatherPxpyArgs *a, void *stream);
+
+/* mpf_sample_pdf   rendering_utils.py:90-139 with the draws u handed in.  Per row (b, n) of S values v and S weights w, in f32, every operation
+ *                  rounded on its own:  edges e[0] = v[0], e[k] = (v[k] + v[k-1]) * 0.5, e[S] = v[S-1];  cdf c[0] = 0, c[k+1] = c[k] + w[k] / (sum w + 1e-5),
+ *                  the cdf added one element at a time in order with the running sum kept in f64 and every entry rounded to f32 (torch's CPU cumsum), sum w
+ *                  the correctly rounded sum (added in f64, rounded once);  per draw u: i = the first index with c[i] > u (S + 1 if none), lo = max(i - 1, 0),
+ *                  hi = min(i, S), t = (u - c[lo]) / max(c[hi] - c[lo], 1e-5), replaced by 0.5 where c[hi] - c[lo] <= 1e-4;  out = e[lo] + t * (e[hi] - e[lo]).
+ * values may be contiguous (values_row_stride = S, values_batch_stride = N * S) or expanded over the rays (values_row_stride = 0: one row of S per
+ * batch entry, values_batch_stride floats apart), which is read in place.
+ * Limits: 1 <= S <= MPF_SAMPLE_PDF_MAX_S; 1 <= n_samples <= MPF_SAMPLE_PDF_MAX_SAMPLES; B * N * max(S, n_samples) below 2^31.  No atomics: identical
+ * bytes on every run. */
+#define MPF_SAMPLE_PDF_MAX_S 128
+#define MPF_SAMPLE_PDF_MAX_SAMPLES 128
+typedef struct MpfSamplePdfArgs {
+    const float *values;             /* [B,1,N,S], or its expanded form (see above) */
+    const float *weights;            /* [B,1,N,S] */
+    const float *u;                  /* [B,1,N,n_samples] */
+    float *out;                      /* [B,1,N,n_samples], written */
+    long long values_batch_stride;   /* floats between two batch entries of values */
+    long long values_row_stride;     /* S, or 0 */
+    int B, N, S, n_samples;
+} MpfSamplePdfArgs;
+int mpf_sample_pdf(const MpfSamplePdfArgs *a, void *stream);
+
+/* mpf_disp_consistency       mpi_rendering.py:180-210.  Per source pixel (x, y) of batch entry b, in f32:  r = K_src_inv (x, y, 1);  depth = 1 / disparity_src;
+ *                            p = G_tgt_src (r * depth, 1);  q = K_tgt p[:3];  (px, py) = q.xy / q.z;  mask = 0 <= px <= W - 1 and 0 <= py <= H - 1 (false with
+ *                            NaN);  diff = |1 / p.z - disparity_tgt[b, index(py, H), index(px, W)]|;  loss = sum over the mask of diff / count.  p.z's sign is
+ *                            not looked at.  The sum: wave butterfly, one LDS slot per wave, per-block partials, then a double sum in block order - no atomics,
+ *                            identical bits on every run; count is an exact integer.  count = 0 gives NaN.  The workspace keeps sum and count for the backward.
+ * mpf_disp_consistency_bwd   with s = sign(1 / p.z - disparity_tgt[idx]) and g = grad_loss[0]:  grad_disparity_src = g s / count * (-1 / p.z^2) * (G[2,:3] . r) *
+ *                            (-1 / disparity_src^2), one store per pixel (0 outside the mask; reproducible);  grad_disparity_tgt[idx] += -g s / count, float
+ *                            atomic adds into a buffer the caller zeroed (source pixels that share a target pixel decide its last bits by their order).
+ *                            Either gradient pointer may be NULL, not both.  The workspace is the forward's, untouched since.
+ * Limits: B <= 65535; B * H * W below 2^31. */
+typedef struct MpfDispConsistencyArgs {
+    const float *K_src_inv;          /* [B,3,3] on the device */
+    const float *G_tgt_src;          /* [B,4,4] on the device */
+    const float *K_tgt;              /* [B,3,3] on the device */
+    const float *disparity_src;      /* [B,1,H,W] */
+    const float *disparity_tgt;      /* [B,1,H,W] */
+    float *loss;                     /* [1], written by mpf_disp_consistency */
+    const float *grad_loss;          /* [1] on the device; read by mpf_disp_consistency_bwd */
+    float *grad_disparity_src;       /* [B,1,H,W], written by mpf_disp_consistency_bwd, or NULL */
+    float *grad_disparity_tgt;       /* [B,1,H,W], added into by mpf_disp_consistency_bwd, or NULL */
+    void *workspace;                 /* mpf_disp_consistency_workspace(B, H, W) bytes, 16-byte aligned: [0] f64 sum, [8] i64 count, then the partials */
+    size_t workspace_bytes;
+    int B, H, W;
+} MpfDispConsistencyArgs;
+size_t mpf_disp_consistency_workspace(int B, int H, int W);              /* 0 for a shape the call refuses */
+int mpf_disp_consistency(const MpfDispConsistencyArgs *a, void *stream);
+int mpf_disp_consistency_bwd(const MpfDispConsistencyArgs *a, void *stream);
 
 /* The optimizer tail of RAFT/train.py (train.py:178-181: clip_grad_norm_, AdamW.step) over a whole parameter set, as one multi-tensor path:
  * the global gradient norm, the clip coefficient and torch's single-tensor AdamW update, without host synchronisation.  All tensors f32.

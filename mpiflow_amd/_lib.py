@@ -228,6 +228,29 @@ class MpfBilateralArgs(ctypes.Structure):
                 ("w", c_i), ("mask_shared", c_i), ("num_iter", c_i), ("filter_size", c_i * BILATERAL_MAX_ITER), ("depth_threshold", ctypes.c_double)]
 
 
+PXPY_F32, PXPY_I64 = 0, 1       # MPF_PXPY_F32 / _I64
+SAMPLE_PDF_MAX_S = 128          # MPF_SAMPLE_PDF_MAX_S
+SAMPLE_PDF_MAX_SAMPLES = 128    # MPF_SAMPLE_PDF_MAX_SAMPLES
+
+
+class MpfGatherPxpyArgs(ctypes.Structure):
+    """struct MpfGatherPxpyArgs of include/mpiflow_hip.h: gather_pixel_by_pxpy and its scatter-add adjoint."""
+    _fields_ = [("img", c_p), ("pxpy", c_p), ("out", c_p), ("grad_out", c_p), ("grad_img", c_p), ("pxpy_dtype", c_i), ("B", c_i), ("C", c_i), ("H", c_i),
+                ("W", c_i), ("N", c_i)]
+
+
+class MpfSamplePdfArgs(ctypes.Structure):
+    """struct MpfSamplePdfArgs of include/mpiflow_hip.h: sample_pdf with the draws handed in."""
+    _fields_ = [("values", c_p), ("weights", c_p), ("u", c_p), ("out", c_p), ("values_batch_stride", ctypes.c_longlong),
+                ("values_row_stride", ctypes.c_longlong), ("B", c_i), ("N", c_i), ("S", c_i), ("n_samples", c_i)]
+
+
+class MpfDispConsistencyArgs(ctypes.Structure):
+    """struct MpfDispConsistencyArgs of include/mpiflow_hip.h: disparity_consistency_src_to_tgt, forward and backward."""
+    _fields_ = [("K_src_inv", c_p), ("G_tgt_src", c_p), ("K_tgt", c_p), ("disparity_src", c_p), ("disparity_tgt", c_p), ("loss", c_p), ("grad_loss", c_p),
+                ("grad_disparity_src", c_p), ("grad_disparity_tgt", c_p), ("workspace", c_p), ("workspace_bytes", c_sz), ("B", c_i), ("H", c_i), ("W", c_i)]
+
+
 WARM_MAX_HW = 65536             # MPF_WARM_MAX_HW
 WARM_MAX_NHW = 1 << 22          # MPF_WARM_MAX_NHW
 
@@ -341,6 +364,12 @@ SIGNATURES = {
     "mpf_sparse_bilateral_workspace": (c_sz, [c_i, c_i, c_i, c_i]),
     "mpf_sparse_bilateral_rank": (c_i, [c_i]),
     "mpf_sparse_bilateral": (c_i, [ctypes.POINTER(MpfBilateralArgs), c_p]),
+    "mpf_gather_pxpy": (c_i, [ctypes.POINTER(MpfGatherPxpyArgs), c_p]),
+    "mpf_gather_pxpy_bwd": (c_i, [ctypes.POINTER(MpfGatherPxpyArgs), c_p]),
+    "mpf_sample_pdf": (c_i, [ctypes.POINTER(MpfSamplePdfArgs), c_p]),
+    "mpf_disp_consistency_workspace": (c_sz, [c_i, c_i, c_i]),
+    "mpf_disp_consistency": (c_i, [ctypes.POINTER(MpfDispConsistencyArgs), c_p]),
+    "mpf_disp_consistency_bwd": (c_i, [ctypes.POINTER(MpfDispConsistencyArgs), c_p]),
     "mpf_adamw_workspace": (c_sz, [ctypes.POINTER(MpfOptTensor), c_i]),
     "mpf_grad_norm": (c_i, [ctypes.POINTER(MpfAdamWArgs), c_p]),
     "mpf_adamw_clipped": (c_i, [ctypes.POINTER(MpfAdamWArgs), c_p]),

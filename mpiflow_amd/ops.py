@@ -1771,6 +1771,173 @@ def sparse_bilateral_filter(depth, filter_size, depth_threshold=0.04, mask=None,
     return out
 
 
+def _gather_pxpy_args(who, pxpy, B, C, H, W, tensors):
+    """MpfGatherPxpyArgs with the shape and pxpy set: pxpy [B,2,N] float32 or int64, contiguous; the call's limits; the device last"""
+    p = check_tensor(pxpy, "pxpy", who, (B, 2, None), "[B,2,N]", dtypes=(torch.float32, torch.int64))
+    N = p.shape[2]
+    if not 1 <= B <= 65535 or min(C, H, W, N) < 1 or B * C * H * W >= 1 << 31 or B * C * N >= 1 << 31:
+        raise _lib.MpiFlowHipError("%s: 1..65535 images, at least one channel, pixel and point, and B * C * H * W and B * C * N below 2^31 "
+                                   "(got B, C, H, W, N = %d, %d, %d, %d, %d)" % (who, B, C, H, W, N))
+    tensors["pxpy"] = p
+    check_devices(who, tensors)
+    a = _lib.MpfGatherPxpyArgs()
+    a.pxpy, a.pxpy_dtype = p.data_ptr(), _lib.PXPY_F32 if p.dtype == torch.float32 else _lib.PXPY_I64
+    a.B, a.C, a.H, a.W, a.N = B, C, H, W, N
+    return a
+
+
+@_on_device
+def gather_pixel_by_pxpy(img, pxpy, out=None):
+    """mpf_gather_pxpy: out[b,c,i] = img[b,c,y_i,x_i] with (x_i, y_i) = pxpy[b,:,i] rounded (ties to even) and clamped to the frame - the reference's
+    gather_pixel_by_pxpy (utils/mpi/rendering_utils.py:26-43).  img [B,C,H,W] float32, pxpy [B,2,N] float32 or int64 -> [B,C,N].  A coordinate that is
+    NaN or -inf reads index 0, +inf the last index.  Contiguous, on the GPU, or MpiFlowHipError.  Asynchronous on the current stream."""
+    who = "gather_pixel_by_pxpy"
+    im = check_tensor(img, "img", who, 4, "[B,C,H,W]")
+    B, C, H, W = im.shape
+    tensors = dict(img=im)
+    if out is not None:
+        N = pxpy.shape[2] if isinstance(pxpy, torch.Tensor) and pxpy.dim() == 3 else None
+        tensors["out"] = check_tensor(out, "out", who, (B, C, N), "[B,C,N]")
+    a = _gather_pxpy_args(who, pxpy, B, C, H, W, tensors)
+    if out is None:
+        out = torch.empty((B, C, a.N), dtype=_f32, device=im.device)
+    a.img, a.out = im.data_ptr(), out.data_ptr()
+    _lib.check(_lib.load().mpf_gather_pxpy(ctypes.byref(a), _stream()), "mpf_gather_pxpy")
+    return out
+
+
+@_on_device
+def gather_pixel_by_pxpy_backward(grad_out, pxpy, H, W, grad_img=None):
+    """Adjoint of gather_pixel_by_pxpy with respect to img (mpf_gather_pxpy_bwd): grad_img[b,c,y_i,x_i] += grad_out[b,c,i].  grad_out [B,C,N] ->
+    [B,C,H,W]; grad_img: a zero-initialised buffer to add into (allocated zeroed when None).  The adds are float atomics: where points share a pixel
+    their arrival order decides the last bits of its sum.  pxpy has no gradient."""
+    who = "gather_pixel_by_pxpy_backward"
+    g = check_tensor(grad_out, "grad_out", who, 3, "[B,C,N]")
+    B, C, N = g.shape
+    H, W = operator.index(H), operator.index(W)
+    tensors = dict(grad_out=g)
+    if grad_img is not None:
+        tensors["grad_img"] = check_tensor(grad_img, "grad_img", who, (B, C, H, W), "[B,C,H,W]")
+    a = _gather_pxpy_args(who, pxpy, B, C, H, W, tensors)
+    if a.N != N:
+        raise _lib.MpiFlowHipError("%s: pxpy must be [B,2,N] with grad_out's N = %d (got shape %s)" % (who, N, tuple(pxpy.shape)))
+    if grad_img is None:
+        grad_img = torch.zeros((B, C, H, W), dtype=_f32, device=g.device)
+    a.grad_out, a.grad_img = g.data_ptr(), grad_img.data_ptr()
+    _lib.check(_lib.load().mpf_gather_pxpy_bwd(ctypes.byref(a), _stream()), "mpf_gather_pxpy_bwd")
+    return grad_img
+
+
+@_on_device
+def sample_pdf(values, weights, u, out=None):
+    """mpf_sample_pdf: the reference's sample_pdf (utils/mpi/rendering_utils.py:90-139) with its uniform draws handed in: values, weights [B,1,N,S] and
+    u [B,1,N,n_samples] float32 -> samples [B,1,N,n_samples], as INTEGRATION.md section 21 states it, in one launch without a [B,1,N,S] temporary.
+    1 <= S, n_samples <= 128 and B * N * max(S, n_samples) < 2^31.  weights, u (and out) are contiguous; values is contiguous or expanded over the rays
+    (stride 0 in dim 2, unit stride in dim 3: a per-plane disparity broadcast with .expand), which is read in place.  Forward only.  On the GPU, or
+    MpiFlowHipError.  Identical bytes on every run.  Asynchronous on the current stream."""
+    who = "sample_pdf"
+    w = check_tensor(weights, "weights", who, (None, 1, None, None), "[B,1,N,S]")
+    B, _, N, S = w.shape
+    if not isinstance(values, torch.Tensor):
+        raise _lib.MpiFlowHipError("%s: values must be a torch.Tensor (got %s)" % (who, type(values).__name__))
+    if values.dtype != torch.float32:
+        raise _lib.MpiFlowHipError("%s: values must be float32 (got %s); call .float() on it (the kernels are float32 only)" % (who, values.dtype))
+    if tuple(values.shape) != (B, 1, N, S):
+        raise _lib.MpiFlowHipError("%s: values must be [B,1,N,S] like weights, %s (got shape %s)" % (who, tuple(w.shape), tuple(values.shape)))
+    expanded = not values.is_contiguous() and values.stride(2) == 0 and (S == 1 or values.stride(3) == 1) and (B == 1 or values.stride(0) >= 0)
+    if not values.is_contiguous() and not expanded:
+        raise _lib.MpiFlowHipError("%s: values must be contiguous, or expanded over the rays with stride 0 in dim 2 and unit stride in dim 3 "
+                                   "(got shape %s with strides %s)" % (who, tuple(values.shape), values.stride()))
+    uu = check_tensor(u, "u", who, (B, 1, N, None), "[B,1,N,n_samples]")
+    NS = uu.shape[3]
+    tensors = dict(values=values, weights=w, u=uu)
+    if out is not None:
+        tensors["out"] = check_tensor(out, "out", who, (B, 1, N, NS), "[B,1,N,n_samples]")
+    if not 1 <= S <= _lib.SAMPLE_PDF_MAX_S:
+        raise _lib.MpiFlowHipError("%s: S must be 1..%d (got %d from weights of shape %s)" % (who, _lib.SAMPLE_PDF_MAX_S, S, tuple(w.shape)))
+    if not 1 <= NS <= _lib.SAMPLE_PDF_MAX_SAMPLES:
+        raise _lib.MpiFlowHipError("%s: n_samples must be 1..%d (got %d from u of shape %s)" % (who, _lib.SAMPLE_PDF_MAX_SAMPLES, NS, tuple(uu.shape)))
+    if B < 1 or N < 1 or B * N * max(S, NS) >= 1 << 31:
+        raise _lib.MpiFlowHipError("%s: at least one row, and B * N * max(S, n_samples) below 2^31 (got B, N, S, n_samples = %d, %d, %d, %d)" % (who, B, N, S, NS))
+    check_devices(who, tensors)
+    if out is None:
+        out = torch.empty((B, 1, N, NS), dtype=_f32, device=w.device)
+    a = _lib.MpfSamplePdfArgs()
+    a.values, a.weights, a.u, a.out = values.data_ptr(), w.data_ptr(), uu.data_ptr(), out.data_ptr()
+    a.values_batch_stride = (values.stride(0) if B > 1 else 0) if expanded else N * S
+    a.values_row_stride = 0 if expanded else S
+    a.B, a.N, a.S, a.n_samples = B, N, S, NS
+    _lib.check(_lib.load().mpf_sample_pdf(ctypes.byref(a), _stream()), "mpf_sample_pdf")
+    return out
+
+
+def _disp_consistency_args(who, K_src_inv, disparity_src, G_tgt_src, K_tgt, disparity_tgt, tensors):
+    """MpfDispConsistencyArgs with the five inputs set; `tensors`: the call's further tensors, already checked.  The device last."""
+    ds = check_tensor(disparity_src, "disparity_src", who, (None, 1, None, None), "[B,1,H,W]")
+    B, _, H, W = ds.shape
+    dt = check_tensor(disparity_tgt, "disparity_tgt", who, 4, "[B,1,H,W]")
+    if dt.shape != ds.shape:
+        raise _lib.MpiFlowHipError("%s: disparity_tgt must have disparity_src's shape %s (got %s): frames of two sizes are not provided"
+                                   % (who, tuple(ds.shape), tuple(dt.shape)))
+    Ki = check_tensor(K_src_inv, "K_src_inv", who, (B, 3, 3), "[B,3,3]")
+    G = check_tensor(G_tgt_src, "G_tgt_src", who, (B, 4, 4), "[B,4,4]")
+    Kt = check_tensor(K_tgt, "K_tgt", who, (B, 3, 3), "[B,3,3]")
+    if not 1 <= B <= 65535 or H < 1 or W < 1 or B * H * W >= 1 << 31:
+        raise _lib.MpiFlowHipError("%s: 1..65535 frames of at least one pixel and B * H * W below 2^31 (got B, H, W = %d, %d, %d)" % (who, B, H, W))
+    all_tensors = dict(disparity_src=ds, disparity_tgt=dt, K_src_inv=Ki, G_tgt_src=G, K_tgt=Kt)
+    all_tensors.update(tensors)
+    check_devices(who, all_tensors)
+    a = _lib.MpfDispConsistencyArgs()
+    a.K_src_inv, a.G_tgt_src, a.K_tgt, a.disparity_src, a.disparity_tgt = Ki.data_ptr(), G.data_ptr(), Kt.data_ptr(), ds.data_ptr(), dt.data_ptr()
+    a.B, a.H, a.W = B, H, W
+    return a
+
+
+@_on_device
+def disparity_consistency(K_src_inv, disparity_src, G_tgt_src, K_tgt, disparity_tgt):
+    """mpf_disp_consistency: the reference's disparity_consistency_src_to_tgt (utils/mpi/mpi_rendering.py:180-210) on the standard (x, y, 1) grid:
+    disparity_src, disparity_tgt [B,1,H,W], K_src_inv, K_tgt [B,3,3], G_tgt_src [B,4,4], all float32 on the GPU (the matrices too: nothing crosses
+    to the host) -> (loss, state).  loss: a 0-dim tensor, the mean over the source pixels that project into the target frame of
+    |1 / p.z - disparity_tgt[rounded pixel]|, NaN when there is none; its sum uses no atomics and gives the same bits on every run.  state: what
+    disparity_consistency_backward needs (the call's workspace; its first 16 bytes hold the float64 sum and the int64 count)."""
+    who = "disparity_consistency"
+    a = _disp_consistency_args(who, K_src_inv, disparity_src, G_tgt_src, K_tgt, disparity_tgt, {})
+    lib = _lib.load()
+    dev = disparity_src.device
+    state = torch.empty(int(lib.mpf_disp_consistency_workspace(a.B, a.H, a.W)), dtype=torch.uint8, device=dev)
+    loss = torch.empty((), dtype=_f32, device=dev)
+    a.loss, a.workspace, a.workspace_bytes = loss.data_ptr(), state.data_ptr(), state.numel()
+    _lib.check(lib.mpf_disp_consistency(ctypes.byref(a), _stream()), "mpf_disp_consistency")
+    return loss, state
+
+
+@_on_device
+def disparity_consistency_backward(grad_loss, state, K_src_inv, disparity_src, G_tgt_src, K_tgt, disparity_tgt, want_src=True, want_tgt=True):
+    """mpf_disp_consistency_bwd -> (grad_disparity_src | None, grad_disparity_tgt | None), each [B,1,H,W].  grad_loss: the upstream gradient, a float32
+    tensor of one element on the GPU; state: disparity_consistency's, for the same inputs.  grad_disparity_src is one store per pixel (the same bits on
+    every run); grad_disparity_tgt is scattered with float atomics, so source pixels that land on one target pixel decide its last bits by their order."""
+    who = "disparity_consistency_backward"
+    if not isinstance(grad_loss, torch.Tensor) or grad_loss.numel() != 1:
+        raise _lib.MpiFlowHipError("%s: grad_loss must be a float32 tensor of one element (got %s)"
+                                   % (who, tuple(grad_loss.shape) if isinstance(grad_loss, torch.Tensor) else type(grad_loss).__name__))
+    g = check_tensor(grad_loss, "grad_loss", who, grad_loss.dim())
+    st = check_tensor(state, "state", who, 1, dtypes=(torch.uint8,))
+    if not (want_src or want_tgt):
+        raise _lib.MpiFlowHipError("%s: want_src or want_tgt: one gradient at least" % who)
+    a = _disp_consistency_args(who, K_src_inv, disparity_src, G_tgt_src, K_tgt, disparity_tgt, dict(grad_loss=g, state=st))
+    lib = _lib.load()
+    need = int(lib.mpf_disp_consistency_workspace(a.B, a.H, a.W))
+    if st.numel() < need:
+        raise _lib.MpiFlowHipError("%s: state holds %d bytes, %d needed: it is not disparity_consistency's for these shapes" % (who, st.numel(), need))
+    grad_src = torch.empty_like(disparity_src) if want_src else None
+    grad_tgt = torch.zeros_like(disparity_tgt) if want_tgt else None
+    a.grad_loss, a.workspace, a.workspace_bytes = g.data_ptr(), st.data_ptr(), st.numel()
+    a.grad_disparity_src = grad_src.data_ptr() if want_src else None
+    a.grad_disparity_tgt = grad_tgt.data_ptr() if want_tgt else None
+    _lib.check(lib.mpf_disp_consistency_bwd(ctypes.byref(a), _stream()), "mpf_disp_consistency_bwd")
+    return grad_src, grad_tgt
+
+
 def _stage2_args(who, B, h, w, **tensors):
     """MpfStage2Args with the named fields set; every tensor already checked"""
     if B < 1 or h < 1 or w < 1 or B > 65535 or B * h * w > (1 << 28):

@@ -231,6 +231,43 @@ class TransformXyzFn(Function):
         return torch.stack(out), None
 
 
+class GatherPxpyFn(Function):
+    """ops.gather_pixel_by_pxpy with the gradient of img (mpf_gather_pxpy_bwd: a float-atomic scatter-add).  pxpy (float32 or int64) gets none, as in the
+    reference, which builds the index under torch.no_grad()."""
+
+    @staticmethod
+    def forward(ctx, img, pxpy):
+        ctx.pxpy = pxpy
+        ctx.hw = (img.size(2), img.size(3))
+        return ops.gather_pixel_by_pxpy(img, pxpy)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        return ops.gather_pixel_by_pxpy_backward(g.contiguous(), ctx.pxpy, *ctx.hw), None
+
+
+class DisparityConsistencyFn(Function):
+    """ops.disparity_consistency with the gradients of disparity_src (one store per pixel: reproducible) and disparity_tgt (float-atomic scatter) through
+    mpf_disp_consistency_bwd.  The matrices are constants on the device; count and the upstream gradient stay there too: no host synchronisation."""
+
+    @staticmethod
+    def forward(ctx, disparity_src, disparity_tgt, K_src_inv, G_tgt_src, K_tgt):
+        loss, state = ops.disparity_consistency(K_src_inv, disparity_src, G_tgt_src, K_tgt, disparity_tgt)
+        ctx.save_for_backward(disparity_src, disparity_tgt)
+        ctx.consts = (K_src_inv, G_tgt_src, K_tgt, state)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        disparity_src, disparity_tgt = ctx.saved_tensors
+        K_src_inv, G_tgt_src, K_tgt, state = ctx.consts
+        g_src, g_tgt = ops.disparity_consistency_backward(g.to(torch.float32).contiguous(), state, K_src_inv, disparity_src, G_tgt_src, K_tgt, disparity_tgt,
+                                                          want_src=ctx.needs_input_grad[0], want_tgt=ctx.needs_input_grad[1])
+        return g_src, g_tgt, None, None, None
+
+
 class PlaneFlowFn(Function):
     """HomographySample.sample_inverse with the gradient of d_src_B (mpf_plane_flow_bwd).  H_tgt_src, d_host, Kt_t and Kinv_row3 are the host's constants
     of the forward; d_src_B only receives the gradient."""

@@ -6,9 +6,10 @@ each function is a drop-in on its own and reproduces the reference's semantics e
 channels rather than recomputing them).  The fused fast path that never materialises an [S,...] intermediate lives in
 mpiflow_amd.pipeline / utils.utils.render_3dphoto_dynamic.
 
-Also provided although MPI-Flow's generation never takes them: alpha_composition / use_alpha=True (:42-59) and
-get_xyz_from_depth (:157-177).  Not provided: disparity_consistency_src_to_tgt (:180-210), a training loss of the MINE code
-base this module was taken from.
+Also provided although MPI-Flow's generation never takes them: alpha_composition / use_alpha=True (:42-59),
+get_xyz_from_depth (:157-177) and disparity_consistency_src_to_tgt (:180-210), the training loss of the MINE code base this module was
+taken from: one fused pass (mpf_disp_consistency), differentiable with respect to both disparity maps under default grad mode
+(INTEGRATION.md section 21).
 
 Differentiable (HIP backward kernels, mpf_render_bwd.hip, behind the Functions of _autograd.py): plane_volume_rendering,
 plane_volume_rendering_flow, render and render_tgt_rgb_depth, with respect to the plane colours, densities and extra values (rgb_BS3HW, sigma_BS1HW,
@@ -27,7 +28,7 @@ import torch
 from ... import _lib, host_math, ops
 from . import _autograd
 from .homography_sampler import HomographySample
-from .rendering_utils import transform_G_xyz  # noqa: F401  (re-exported like the reference module does)
+from .rendering_utils import transform_G_xyz, sample_pdf, gather_pixel_by_pxpy  # noqa: F401  (re-exported like the reference module does)
 
 
 # ---- provenance tags: which tensors are "the standard ones" ---------------------------------------------------------------------------
@@ -98,6 +99,46 @@ def get_xyz_from_depth(meshgrid_homo, depth, K_inv):
     B, _, H_d, W_d = depth.size()
     assert H == H_d and W == W_d
     return torch.stack([ops.backproject(depth[b, 0], K_inv[b])[:3].reshape(3, H, W) for b in range(B)])
+
+
+def _require_standard_meshgrid(who, meshgrid_homo, H, W):
+    """meshgrid_homo must be HomographySample's 3xHxW grid of (x, y, 1) for this frame: the kernel generates the coordinates itself.  A grid on the host is
+    compared there; one on the GPU by its size alone, so that nothing synchronises."""
+    if not isinstance(meshgrid_homo, torch.Tensor) or tuple(meshgrid_homo.shape) != (3, H, W):
+        raise _lib.MpiFlowHipError("%s: meshgrid_homo must be the standard 3xHxW grid of (x, y, 1) for the %dx%d frame of disparity_src (got %s)"
+                                   % (who, H, W, tuple(meshgrid_homo.shape) if isinstance(meshgrid_homo, torch.Tensor) else type(meshgrid_homo).__name__))
+    if not meshgrid_homo.is_cuda:
+        std = HomographySample.grid_generation(H, W, meshgrid_homo.device).permute(2, 0, 1)
+        if not torch.equal(meshgrid_homo.to(torch.float32), std):
+            raise _lib.MpiFlowHipError("%s: meshgrid_homo must be the standard grid of (x, y, 1), x = 0..W-1, y = 0..H-1 (HomographySample(H, W).meshgrid): "
+                                       "the kernel generates the coordinates itself" % who)
+
+
+def disparity_consistency_src_to_tgt(meshgrid_homo, K_src_inv, disparity_src, G_tgt_src, K_tgt, disparity_tgt):
+    """mean over the source pixels that project into the target frame of |1 / z_tgt - disparity_tgt[rounded target pixel]|   (reference :180-210)
+
+    :param meshgrid_homo: 3xHxW - the standard (x, y, 1) grid of HomographySample for the frame's size (the kernel generates the coordinates)
+    :param K_src_inv: Bx3x3
+    :param disparity_src: Bx1xHxW float32 on the GPU
+    :param G_tgt_src: Bx4x4
+    :param K_tgt: Bx3x3
+    :param disparity_tgt: Bx1xHxW float32 on the GPU, the size of disparity_src
+    :return: a 0-dim float32 tensor on the GPU; NaN when no source pixel lands in the target frame (the mean of an empty selection)
+
+    One fused pass (mpf_disp_consistency) with the matrices on the device: loss and count stay there, nothing synchronises with the host.  Differentiable
+    with respect to disparity_src (one store per pixel, the same bits on every run) and disparity_tgt (a float-atomic scatter: source pixels that land on
+    one target pixel decide its last bits by their order) under default grad mode - plane_geometry_grad() is not needed.  K_src_inv, G_tgt_src or K_tgt
+    requiring grad is refused."""
+    who = "disparity_consistency_src_to_tgt"
+    _autograd.refuse_geometry(who, (), K_src_inv=K_src_inv, G_tgt_src=G_tgt_src, K_tgt=K_tgt)
+    if isinstance(disparity_src, torch.Tensor) and disparity_src.dim() == 4:
+        _require_standard_meshgrid(who, meshgrid_homo, disparity_src.size(2), disparity_src.size(3))
+    dev = disparity_src.device if isinstance(disparity_src, torch.Tensor) else None
+    mats = [m.detach().to(dev, torch.float32).contiguous() if isinstance(m, torch.Tensor) else m for m in (K_src_inv, G_tgt_src, K_tgt)]
+    if _autograd.wants_grad(disparity_src, disparity_tgt):
+        _autograd.check_values(who, disparity_src=disparity_src, disparity_tgt=disparity_tgt)
+        return _autograd.DisparityConsistencyFn.apply(disparity_src, disparity_tgt, *mats)
+    return ops.disparity_consistency(mats[0], disparity_src.detach(), mats[1], mats[2], disparity_tgt.detach())[0]
 
 
 def plane_volume_rendering(rgb_BS3HW, sigma_BS1HW, xyz_BS3HW, src_sigma_BS1HW, src_flow_BS2HW, src_xyz_BS3HW,
