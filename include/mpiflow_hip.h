@@ -50,7 +50,8 @@ extern "C" {
                              mpf_rasterize_grid_workspace with MpfMeshVertexArgs / MpfMeshRasterArgs, and now mpf_canny and mpf_canny_workspace
                              with MpfCannyArgs and the four mpf_stage2_* calls with MpfStage2Args, and now mpf_sparse_bilateral, mpf_sparse_bilateral_workspace
                              and mpf_sparse_bilateral_rank with MpfBilateralArgs, and now mpf_gather_pxpy, mpf_gather_pxpy_bwd, mpf_sample_pdf,
-                             mpf_disp_consistency, its _bwd and _workspace calls with MpfGatherPxpyArgs / MpfSamplePdfArgs / MpfDispConsistencyArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
+                             mpf_disp_consistency, its _bwd and _workspace calls with MpfGatherPxpyArgs / MpfSamplePdfArgs / MpfDispConsistencyArgs, and now mpf_flow_warp,
+                             mpf_flow_warp_bwd and mpf_flow_warp_workspace with MpfFlowWarpArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
 
 /* d_params layout (floats):
  *   [0..8]   K_src^-1 (3x3 row-major)            [9..20]  G_tgt_src rows 0..2 (3x4 row-major: R | t)
@@ -1042,6 +1043,49 @@ typedef struct MpfDispConsistencyArgs {
 size_t mpf_disp_consistency_workspace(int B, int H, int W);              /* 0 for a shape the call refuses */
 int mpf_disp_consistency(const MpfDispConsistencyArgs *a, void *stream);
 int mpf_disp_consistency_bwd(const MpfDispConsistencyArgs *a, void *stream);
+
+/* The reference's backward warps by a flow field (utils/transform.py:60-111); INTEGRATION.md section 22 states both (tests/flow_warp_restated.py
+ * restates them in float64).  All tensors f32 and contiguous; everything is validated before anything is launched (MPF_ERR_BAD_ARGUMENT); nothing
+ * synchronises with the host.  Per pixel (x, y) of batch entry b with (u, v) = flow[b,:,y,x], in f32, every operation rounded on its own:
+ *   MPF_FLOW_WARP_WARP   warp():  g = 2 * (x + u) / max(W - 1, 1) - 1;  ix = ((g + 1) * W - 1) / 2  (normalised for align_corners=True, sampled
+ *                        at grid_sample's default False, as the reference does);  zero padding: a tap outside the image contributes 0;
+ *                        mask = the sum of the weights of the taps inside;  d ix / d u = W / max(W - 1, 1).
+ *   MPF_FLOW_WARP_RIFE   warp_rife():  g = lin_w[x] + u / ((W - 1) / 2) with lin_w = torch.linspace(-1, 1, W) handed in;  ix = (g + 1) / 2 * (W - 1),
+ *                        clamped to [0, W - 1] (border padding; no gradient where ix <= 0 or ix >= W - 1, torch's clip_coordinates_set_grad);
+ *                        d ix / d u = 1 inside the clamp.  No mask.  H, W >= 2.
+ *   both, y likewise.    ix_nw = floor(ix);  nw = (ix_se - ix) * (iy_se - iy), ne = (ix - ix_sw) * (iy_sw - iy), sw = (ix_ne - ix) * (iy - iy_ne),
+ *                        se = (ix - ix_nw) * (iy - iy_nw);  out[b,c,y,x] = x[nw tap] * nw + ... summed nw, ne, sw, se.  A non-finite coordinate
+ *                        samples outside the image (WARP) or at index 0 (RIFE).
+ * mpf_flow_warp       writes out and, where mask is not NULL (WARP only), mask [B,1,H,W].
+ * mpf_flow_warp_bwd   grad_x[tap] += weight * grad_out, float atomic adds into a buffer the caller zeroed (the order of the adds decides its last
+ *                     bits);  grad_flow[b,0] = d ix / d u * sum over c of grad_out * d out / d ix (and [b,1] likewise): one store per pixel, the sum
+ *                     taken per chunk of MPF_FLOW_WARP_CHUNK channels in channel order, the chunks in chunk order - no atomics, identical bytes
+ *                     on every run.  Either gradient pointer may be NULL, not both.  With more than one chunk the chunks run as grid.z slices and
+ *                     grad_flow needs mpf_flow_warp_workspace bytes for their shares; whole != 0 makes one thread walk every chunk instead (no
+ *                     workspace; the same bytes).
+ * Limits: B <= 32767; H * W <= 2^30; B * C * H * W and B * 2 * H * W below 2^31. */
+#define MPF_FLOW_WARP_WARP 0
+#define MPF_FLOW_WARP_RIFE 1
+#define MPF_FLOW_WARP_CHUNK 64
+typedef struct MpfFlowWarpArgs {
+    const float *x;                  /* [B,C,H,W] */
+    const float *flow;               /* [B,2,H,W] */
+    const float *lin_w;              /* [W]: torch.linspace(-1, 1, W); MPF_FLOW_WARP_RIFE only */
+    const float *lin_h;              /* [H]: torch.linspace(-1, 1, H); MPF_FLOW_WARP_RIFE only */
+    float *out;                      /* [B,C,H,W], written by mpf_flow_warp */
+    float *mask;                     /* [B,1,H,W], written by mpf_flow_warp, or NULL */
+    const float *grad_out;           /* [B,C,H,W]; read by mpf_flow_warp_bwd */
+    float *grad_x;                   /* [B,C,H,W], added into by mpf_flow_warp_bwd, or NULL */
+    float *grad_flow;                /* [B,2,H,W], written by mpf_flow_warp_bwd, or NULL */
+    void *workspace;                 /* mpf_flow_warp_workspace(B, C, H, W, whole) bytes; read and written by mpf_flow_warp_bwd for grad_flow */
+    size_t workspace_bytes;
+    int mode;                        /* MPF_FLOW_WARP_WARP / _RIFE */
+    int B, C, H, W;
+    int whole;                       /* 0: channel chunks as grid.z slices; else one thread per pixel walks every channel */
+} MpfFlowWarpArgs;
+size_t mpf_flow_warp_workspace(int B, int C, int H, int W, int whole);    /* 0 where none is needed, and for a shape the calls refuse */
+int mpf_flow_warp(const MpfFlowWarpArgs *a, void *stream);
+int mpf_flow_warp_bwd(const MpfFlowWarpArgs *a, void *stream);
 
 /* The optimizer tail of RAFT/train.py (train.py:178-181: clip_grad_norm_, AdamW.step) over a whole parameter set, as one multi-tensor path:
  * the global gradient norm, the clip coefficient and torch's single-tensor AdamW update, without host synchronisation.  All tensors f32.

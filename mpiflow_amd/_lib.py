@@ -251,6 +251,17 @@ class MpfDispConsistencyArgs(ctypes.Structure):
                 ("grad_disparity_src", c_p), ("grad_disparity_tgt", c_p), ("workspace", c_p), ("workspace_bytes", c_sz), ("B", c_i), ("H", c_i), ("W", c_i)]
 
 
+FLOW_WARP_WARP, FLOW_WARP_RIFE = 0, 1       # MPF_FLOW_WARP_WARP / _RIFE
+FLOW_WARP_CHUNK = 64                        # MPF_FLOW_WARP_CHUNK
+
+
+class MpfFlowWarpArgs(ctypes.Structure):
+    """struct MpfFlowWarpArgs of include/mpiflow_hip.h: the backward warps by a flow field (warp, warp_rife), forward and adjoint."""
+    _fields_ = [("x", c_p), ("flow", c_p), ("lin_w", c_p), ("lin_h", c_p), ("out", c_p), ("mask", c_p), ("grad_out", c_p), ("grad_x", c_p),
+                ("grad_flow", c_p), ("workspace", c_p), ("workspace_bytes", c_sz), ("mode", c_i), ("B", c_i), ("C", c_i), ("H", c_i), ("W", c_i),
+                ("whole", c_i)]
+
+
 WARM_MAX_HW = 65536             # MPF_WARM_MAX_HW
 WARM_MAX_NHW = 1 << 22          # MPF_WARM_MAX_NHW
 
@@ -370,6 +381,9 @@ SIGNATURES = {
     "mpf_disp_consistency_workspace": (c_sz, [c_i, c_i, c_i]),
     "mpf_disp_consistency": (c_i, [ctypes.POINTER(MpfDispConsistencyArgs), c_p]),
     "mpf_disp_consistency_bwd": (c_i, [ctypes.POINTER(MpfDispConsistencyArgs), c_p]),
+    "mpf_flow_warp_workspace": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
+    "mpf_flow_warp": (c_i, [ctypes.POINTER(MpfFlowWarpArgs), c_p]),
+    "mpf_flow_warp_bwd": (c_i, [ctypes.POINTER(MpfFlowWarpArgs), c_p]),
     "mpf_adamw_workspace": (c_sz, [ctypes.POINTER(MpfOptTensor), c_i]),
     "mpf_grad_norm": (c_i, [ctypes.POINTER(MpfAdamWArgs), c_p]),
     "mpf_adamw_clipped": (c_i, [ctypes.POINTER(MpfAdamWArgs), c_p]),

@@ -1938,6 +1938,97 @@ def disparity_consistency_backward(grad_loss, state, K_src_inv, disparity_src, G
     return grad_src, grad_tgt
 
 
+_flow_warp_lin = {}
+
+
+def flow_warp_linspace(device, H, W):
+    """warp_rife's grids: (torch.linspace(-1, 1, W), torch.linspace(-1, 1, H)) on `device`, made by torch once per (device, H, W) and kept, as the
+    reference keeps its backwarp_tenGrid.  The kernel reads them; it does not re-derive linspace."""
+    key = (str(device), int(H), int(W))
+    if key not in _flow_warp_lin:
+        _flow_warp_lin[key] = (torch.linspace(-1.0, 1.0, int(W), dtype=_f32, device=device), torch.linspace(-1.0, 1.0, int(H), dtype=_f32, device=device))
+    return _flow_warp_lin[key]
+
+
+def _flow_warp_args(who, x, flow, mode, tensors, whole=False):
+    """MpfFlowWarpArgs with x, flow, the mode, the shape and (warp_rife) the linspace grids set; `tensors`: the call's further [B,C,H,W] tensors by
+    name.  x's own checks, flow's, the others', the mode's limits, the device last."""
+    xx = check_tensor(x, "x", who, 4, "[B,C,H,W]")
+    B, C, H, W = xx.shape
+    if isinstance(flow, torch.Tensor) and flow.dim() == 4 and flow.shape[0] != B:
+        raise _lib.MpiFlowHipError("%s: flow must have x's batch size %d (got shape %s)" % (who, B, tuple(flow.shape)))
+    fl = check_tensor(flow, "flow", who, (B, 2, H, W), "[B,2,H,W] with x's B, H, W = %d, %d, %d" % (B, H, W))
+    checked = dict(x=xx, flow=fl)
+    for name, (t, shape, layout) in tensors.items():
+        if t is not None:
+            checked[name] = check_tensor(t, name, who, shape(B, C, H, W), layout)
+    if mode not in (_lib.FLOW_WARP_WARP, _lib.FLOW_WARP_RIFE):
+        raise _lib.MpiFlowHipError("%s: mode must be FLOW_WARP_WARP (0) or FLOW_WARP_RIFE (1) (got %r)" % (who, mode))
+    if not 1 <= B <= 32767 or min(C, H, W) < 1 or H * W > 1 << 30 or B * C * H * W >= 1 << 31 or B * 2 * H * W >= 1 << 31:
+        raise _lib.MpiFlowHipError("%s: 1..32767 images of at least one channel and pixel, H * W at most 2^30 and B * C * H * W and B * 2 * H * W below "
+                                   "2^31 (got B, C, H, W = %d, %d, %d, %d)" % (who, B, C, H, W))
+    if mode == _lib.FLOW_WARP_RIFE and (H < 2 or W < 2):
+        raise _lib.MpiFlowHipError("%s: warp_rife needs H and W of at least 2 (got H, W = %d, %d): its scale (W - 1) / 2 is 0 at one pixel" % (who, H, W))
+    check_devices(who, checked)
+    a = _lib.MpfFlowWarpArgs()
+    a.x, a.flow, a.mode, a.whole = xx.data_ptr(), fl.data_ptr(), mode, 1 if whole else 0
+    a.B, a.C, a.H, a.W = B, C, H, W
+    keep = None
+    if mode == _lib.FLOW_WARP_RIFE:
+        keep = flow_warp_linspace(xx.device, H, W)
+        a.lin_w, a.lin_h = keep[0].data_ptr(), keep[1].data_ptr()
+    return a, keep
+
+
+_BCHW = (lambda B, C, H, W: (B, C, H, W), "[B,C,H,W] like x")
+
+
+@_on_device
+def flow_warp(x, flow, mode, want_mask, out=None, whole=False):
+    """mpf_flow_warp: the reference's backward warp of x [B,C,H,W] by flow [B,2,H,W] (utils/transform.py:60-111) in one pass - a pixel's taps are
+    built once and used for every channel and for the mask.  mode: _lib.FLOW_WARP_WARP (warp(): zero padding, the reference's mixed align_corners)
+    or _lib.FLOW_WARP_RIFE (warp_rife(): border padding, align_corners=True).  -> (out [B,C,H,W], mask [B,1,H,W] or None); want_mask is for
+    FLOW_WARP_WARP only: the sum of the weights of the taps inside the image.  float32, contiguous, on one GPU, or MpiFlowHipError before anything is
+    launched.  whole: one thread per pixel walks every channel instead of 64-channel grid.z slices (a tuning knob; the same bytes).  Identical bytes
+    on every run.  Asynchronous on the current stream."""
+    who = "flow_warp"
+    if want_mask and mode == _lib.FLOW_WARP_RIFE:
+        raise _lib.MpiFlowHipError("%s: warp_rife has no mask (want_mask with FLOW_WARP_RIFE)" % who)
+    a, keep = _flow_warp_args(who, x, flow, mode, dict(out=(out,) + _BCHW), whole)
+    if out is None:
+        out = torch.empty_like(x)
+    mask = torch.empty((a.B, 1, a.H, a.W), dtype=_f32, device=x.device) if want_mask else None
+    a.out, a.mask = out.data_ptr(), mask.data_ptr() if want_mask else None
+    _lib.check(_lib.load().mpf_flow_warp(ctypes.byref(a), _stream()), "mpf_flow_warp")
+    del keep
+    return out, mask
+
+
+@_on_device
+def flow_warp_backward(x, flow, g_out, mode, want_x=True, want_flow=True, grad_x=None, whole=False):
+    """mpf_flow_warp_bwd -> (grad_x [B,C,H,W] | None, grad_flow [B,2,H,W] | None) for the upstream gradient g_out [B,C,H,W] of flow_warp's out (the
+    mask has no gradient).  grad_x is scattered with float atomic adds into a zeroed buffer (grad_x: a zero-initialised one to add into), so the order
+    of the adds decides its last bits; grad_flow is one store per pixel, summed over the channels in a fixed order without atomics: identical bytes
+    on every run, and with whole=True (one thread walks every channel; no workspace) as without."""
+    who = "flow_warp_backward"
+    if not (want_x or want_flow):
+        raise _lib.MpiFlowHipError("%s: want_x or want_flow: one gradient at least" % who)
+    a, keep = _flow_warp_args(who, x, flow, mode, dict(g_out=(g_out,) + _BCHW, grad_x=(grad_x if want_x else None,) + _BCHW), whole)
+    lib = _lib.load()
+    if want_x and grad_x is None:
+        grad_x = torch.zeros_like(x)
+    grad_flow = torch.empty_like(flow) if want_flow else None
+    need = int(lib.mpf_flow_warp_workspace(a.B, a.C, a.H, a.W, a.whole)) if want_flow else 0
+    ws = torch.empty(need, dtype=torch.uint8, device=x.device) if need else None
+    a.grad_out = g_out.data_ptr()
+    a.grad_x = grad_x.data_ptr() if want_x else None
+    a.grad_flow = grad_flow.data_ptr() if want_flow else None
+    a.workspace, a.workspace_bytes = (ws.data_ptr(), need) if need else (None, 0)
+    _lib.check(lib.mpf_flow_warp_bwd(ctypes.byref(a), _stream()), "mpf_flow_warp_bwd")
+    del ws, keep                                                # stream-ordered allocator: a later allocation on this stream queues behind the kernels
+    return (grad_x if want_x else None), grad_flow
+
+
 def _stage2_args(who, B, h, w, **tensors):
     """MpfStage2Args with the named fields set; every tensor already checked"""
     if B < 1 or h < 1 or w < 1 or B > 65535 or B * h * w > (1 << 28):
