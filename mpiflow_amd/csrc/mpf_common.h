@@ -33,4 +33,4 @@ static inline int mpf_launch_status(const char *what)
     return 0;
 }
 
-static inline bool mpf_aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
+__host__ __device__ static inline bool mpf_aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }

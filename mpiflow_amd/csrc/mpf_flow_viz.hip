@@ -19,6 +19,7 @@
 //
 // The only value-dependent address is the wheel entry (LDS, index clamped).  Flow and frame rows have any width and alignment: scalar loads.
 #include "mpf_common.h"
+#include "mpf_reduce.h"
 
 #define VIZ_THREADS 256
 #define VIZ_WAVES 4
@@ -38,13 +39,6 @@ struct VizDev {
     double wheel[VIZ_NCOLS * 3];                   // make_colorwheel() / 255.0
 };
 
-__device__ __forceinline__ float viz_wave_max(float v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
-    return v;
-}
-
 // np.clip(x, 0, clip_flow) (upstream clips to [0, clip_flow], not to [-clip_flow, clip_flow])
 __device__ __forceinline__ float viz_clip(const VizDev &a, float x) { return a.clip ? fminf(fmaxf(x, 0.0f), a.clip_flow) : x; }
 
@@ -60,7 +54,7 @@ __global__ __launch_bounds__(VIZ_THREADS) void k_flow_rad_max(const VizDev a)
         const float u = viz_clip(a, pu[i]), v = viz_clip(a, pv[i]);
         m = fmaxf(m, sqrtf(u * u + v * v));
     }
-    m = viz_wave_max(m);
+    m = mpf_wave_max(m);
     if (lane == 0) sM[wave] = m;
     __syncthreads();
     if (threadIdx.x == 0) a.slots[(size_t)n * gridDim.x + blockIdx.x] = fmaxf(fmaxf(sM[0], sM[1]), fmaxf(sM[2], sM[3]));
@@ -101,7 +95,7 @@ __global__ __launch_bounds__(VIZ_THREADS) void k_flow_colour(const VizDev a)
         const float *slot = a.slots + (size_t)(n_first + k) * a.nslots;
         float m = 0.0f;
         for (int b = lane; b < a.nslots; b += 64) m = fmaxf(m, slot[b]);
-        m = viz_wave_max(m);
+        m = mpf_wave_max(m);
         if (lane == 0) sD[k] = m + 1e-5f;
     }
     __syncthreads();

@@ -30,6 +30,7 @@
 #include <string.h>
 #include "mpf_common.h"
 #include "mpf_math.h"
+#include "mpf_reduce.h"
 
 static int g_fw_prio = 0;       // mpf_tune("chain_prio", 0..3): s_setprio of the sort / resolve / mask kernels (they run underneath a pair launch)
 #define MPF_FW_SETPRIO(p) do { if ((p) == 1) __builtin_amdgcn_s_setprio(1); else if ((p) == 2) __builtin_amdgcn_s_setprio(2); else if ((p) == 3) __builtin_amdgcn_s_setprio(3); } while (0)
@@ -467,8 +468,7 @@ k_fw_bucket(const uint32_t *__restrict__ keys_in, const uint32_t *__restrict__ v
     // this bucket's slice [start, start + n) of the sorted-by-high-digit arrays: start = sum of the totals of the buckets below
     uint32_t part = 0;
     for (uint32_t k = tid; k < b; k += SORT_THREADS) part += totals[k];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off);
+    part = mpf_wave_sum(part);
     if (lane == 0) red[wave] = part;
 #pragma unroll
     for (int k = 0; k < DPT; ++k) hcount[tid + k * SORT_THREADS] = 0;
@@ -600,19 +600,6 @@ k_fw_bucket(const uint32_t *__restrict__ keys_in, const uint32_t *__restrict__ v
 #define FWG_LB 8                  // a bucket = 256 consecutive targets, resolved by one wave
 #define FWG_CAP 512               // visitors a wave keeps in LDS per chunk; a bucket with more is streamed through in chunks
 
-MPF_DEV uint32_t fwg_wave_min(uint32_t v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) { const uint32_t o = __shfl_xor(v, off); v = o < v ? o : v; }
-    return v;
-}
-MPF_DEV uint32_t fwg_wave_max(uint32_t v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) { const uint32_t o = __shfl_xor(v, off); v = o > v ? o : v; }
-    return v;
-}
-
 // Pass 1: the key (target) of every source - computed by the projection of moving_obj.py:29-124 (PROJ) or from the caller's idx / idy -, and the
 // [min, max] key of every 64-source slab and every 1024-source tile.  Slabs / tiles beyond N get the empty range [0xFFFFFFFF, 0].
 template <bool PROJ>
@@ -652,8 +639,8 @@ k_fw_keys_ranges(const float *__restrict__ disp, const MpfMoProj m, const float 
                 keys[n] = key;
                 kmin = kmax = key;
             }
-            kmin = fwg_wave_min(kmin);
-            kmax = fwg_wave_max(kmax);
+            kmin = mpf_wave_min(kmin);
+            kmax = mpf_wave_max(kmax);
             if (lane == 0) {
                 const uint32_t slab = tile * 16 + it * 4 + wave;
                 slab_min[slab] = kmin;

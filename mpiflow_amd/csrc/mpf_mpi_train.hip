@@ -25,6 +25,7 @@
 // No workgroup waits for another, every loop is bounded by S, NS or C, and every index that depends on a tensor's value is clamped to its frame.
 #include "mpf_common.h"
 #include "mpf_math.h"
+#include "mpf_reduce.h"
 #include <math.h>
 
 #define MPT_THREADS 256
@@ -243,10 +244,8 @@ __global__ __launch_bounds__(MPT_THREADS) void k_dispc_fwd(const float *__restri
             c = 1;
         }
     }
-    for (int m = 32; m >= 1; m >>= 1) {
-        v += __shfl_xor(v, m);
-        c += __shfl_xor(c, m);
-    }
+    v = mpf_wave_sum(v), c = mpf_wave_sum(c);
+    // the float sum and the int count share one barrier, so the block step is spelt out here and not two mpf_block_sums calls
     if ((threadIdx.x & 63u) == 0) s_sum[threadIdx.x >> 6] = v, s_cnt[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -26,6 +26,7 @@
 // is torch's threshold_backward.  No address depends on a tensor's values.
 #include "mpf_common.h"
 #include "mpf_math.h"
+#include "mpf_reduce.h"
 
 #define NORM_THREADS 256
 #define NORM_WAVES (NORM_THREADS / 64)
@@ -125,14 +126,6 @@ __device__ __forceinline__ void norm_merge_stats(const NormTermDev &t, const Nor
     }
 }
 
-// the sum of v over wave 0's lanes in a fixed tree
-__device__ __forceinline__ double norm_wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 // the sums of up to four values over the workgroup, in a fixed order, to every thread
 template <int K>
 __device__ __forceinline__ void norm_block_sum(double (&v)[K], NormShared &sh)
@@ -140,7 +133,7 @@ __device__ __forceinline__ void norm_block_sum(double (&v)[K], NormShared &sh)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int e = 0; e < K; ++e) {
-        v[e] = norm_wave_sum(v[e]);
+        v[e] = mpf_wave_sum(v[e]);
         if (lane == 0) sh.red[wave][e] = v[e];
     }
     __syncthreads();
@@ -309,7 +302,7 @@ __device__ __forceinline__ void norm_merge_grads(const NormTermDev &t, const Nor
             const double w = t.w ? (double)t.w[(off / a.chunks) % a.C] : 1.0;
             sa += w * t.gpartials[2 * (size_t)off], sb += w * t.gpartials[2 * (size_t)off + 1];
         }
-        sa = norm_wave_sum(sa), sb = norm_wave_sum(sb);
+        sa = mpf_wave_sum(sa), sb = mpf_wave_sum(sb);
         if (lane == 0) gsum[0] = (float)(sa / s.m), gsum[1] = (float)(sb / s.m);
     }
     if (n == 0 && k == 0 && (t.dw || t.db)) {
@@ -319,7 +312,7 @@ __device__ __forceinline__ void norm_merge_grads(const NormTermDev &t, const Nor
             const int nn = j / a.chunks, off = (nn * a.C + c) * a.chunks + (j - nn * a.chunks);
             sa += t.gpartials[2 * (size_t)off], sb += t.gpartials[2 * (size_t)off + 1];
         }
-        sa = norm_wave_sum(sa), sb = norm_wave_sum(sb);
+        sa = mpf_wave_sum(sa), sb = mpf_wave_sum(sb);
         if (lane == 0) {
             if (t.db) t.db[c] = (float)sa;
             if (t.dw) t.dw[c] = (float)sb;

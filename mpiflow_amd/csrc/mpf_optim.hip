@@ -23,6 +23,7 @@
 #include <math.h>
 #include "mpf_common.h"
 #include "mpf_math.h"             // mpf_load_vec, mpf_store_vec
+#include "mpf_reduce.h"
 
 #define OPT_THREADS 256
 #define OPT_WAVES 4
@@ -61,15 +62,6 @@ __device__ __forceinline__ int opt_find(const OptLaunch &a, unsigned b)
     return lo;
 }
 
-__device__ __forceinline__ bool opt_aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
-
-__device__ __forceinline__ double opt_wave_sum(double v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
 __global__ __launch_bounds__(OPT_THREADS) void k_opt_sumsq(const OptLaunch a)
 {
     __shared__ double sW[OPT_WAVES];
@@ -79,7 +71,7 @@ __global__ __launch_bounds__(OPT_THREADS) void k_opt_sumsq(const OptLaunch a)
     const int n = left < MPF_OPT_CHUNK ? (int)left : MPF_OPT_CHUNK;
     const float *g = a.t[i].grad + base;
     float x[OPT_ROUNDS][OPT_VEC];
-    if (n == MPF_OPT_CHUNK && opt_aligned16(g)) {
+    if (n == MPF_OPT_CHUNK && mpf_aligned16(g)) {
 #pragma unroll
         for (int r = 0; r < OPT_ROUNDS; ++r) mpf_load_vec<OPT_VEC>(g + (r * OPT_THREADS + (int)threadIdx.x) * OPT_VEC, x[r]);
     } else {
@@ -96,15 +88,8 @@ __global__ __launch_bounds__(OPT_THREADS) void k_opt_sumsq(const OptLaunch a)
     for (int r = 0; r < OPT_ROUNDS; ++r)
 #pragma unroll
         for (int e = 0; e < OPT_VEC; ++e) s += (double)x[r][e] * (double)x[r][e];
-    s = opt_wave_sum(s);
-    if ((threadIdx.x & 63) == 0) sW[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double v = sW[0];
-#pragma unroll
-        for (int w = 1; w < OPT_WAVES; ++w) v += sW[w];
-        a.partials[a.partial_base + blockIdx.x] = v;
-    }
+    const double part[1] = {s};
+    mpf_block_sums<OPT_WAVES>(part, 1, sW, a.partials + a.partial_base + blockIdx.x);
 }
 
 // one workgroup: lane t adds partials t, t + 256, ... in that order, then the tree: a fixed order
@@ -114,12 +99,7 @@ __global__ __launch_bounds__(OPT_THREADS) void k_opt_norm_finish(const double *p
     if (n >= 0) {
         double v = 0.0;
         for (int b = threadIdx.x; b < n; b += OPT_THREADS) v += partials[b];
-        sR[threadIdx.x] = v;
-        __syncthreads();
-        for (int m = OPT_THREADS / 2; m >= 1; m >>= 1) {
-            if ((int)threadIdx.x < m) sR[threadIdx.x] += sR[threadIdx.x + m];
-            __syncthreads();
-        }
+        mpf_block_tree_sum<OPT_THREADS>(v, sR);
     }
     if (threadIdx.x == 0) {
         const double sum = n >= 0 ? sR[0] : tail->sumsq;
@@ -140,7 +120,7 @@ __global__ __launch_bounds__(OPT_THREADS) void k_opt_adamw(const OptLaunch a)
     const int n = left < MPF_OPT_CHUNK ? (int)left : MPF_OPT_CHUNK;
     float *pp = a.t[i].param + base, *pm = a.t[i].exp_avg + base, *pv = a.t[i].exp_avg_sq + base, *pg = a.t[i].grad + base;
     const float coef = a.tail->coef;
-    const bool vec = n == MPF_OPT_CHUNK && opt_aligned16(pp) && opt_aligned16(pm) && opt_aligned16(pv) && opt_aligned16(pg);
+    const bool vec = n == MPF_OPT_CHUNK && mpf_aligned16(pp) && mpf_aligned16(pm) && mpf_aligned16(pv) && mpf_aligned16(pg);
     float p[OPT_ROUNDS][OPT_VEC], m[OPT_ROUNDS][OPT_VEC], v[OPT_ROUNDS][OPT_VEC], g[OPT_ROUNDS][OPT_VEC];
     if (vec) {
 #pragma unroll

@@ -22,6 +22,7 @@
 // Memory-bound and small: at 384 x 1280 and B = 8 a batch reads the frames once or twice and writes them once, ~50-70 MB.  The inputs are
 // read through buffer descriptors sized to the frame.
 #include "mpf_common.h"
+#include "mpf_reduce.h"
 #include <algorithm>
 #include <cmath>
 
@@ -136,13 +137,6 @@ __device__ __forceinline__ int contrast_pos(const PhotoDev &s, int j)
     return -1;
 }
 
-__device__ __forceinline__ unsigned wave_sum(unsigned v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // block-wide sums of N per-thread values -> one 64-bit atomicAdd per value (threads 0 .. N-1)
 template <int N>
 __device__ __forceinline__ void block_add(unsigned (&v)[N], unsigned long long *dst)
@@ -151,7 +145,7 @@ __device__ __forceinline__ void block_add(unsigned (&v)[N], unsigned long long *
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int c = 0; c < N; ++c) {
-        v[c] = wave_sum(v[c]);
+        v[c] = mpf_wave_sum(v[c]);
         if (lane == 0) part[wave][c] = v[c];
     }
     __syncthreads();

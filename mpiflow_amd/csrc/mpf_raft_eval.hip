@@ -24,6 +24,7 @@
 #include "mpf_convex.h"
 #include "mpf_math.h"             // mpf_store_vec
 #include "mpf_raft_scale.h"
+#include "mpf_reduce.h"
 #include "mpf_upflow8.h"
 
 #define EVAL_THREADS 256
@@ -131,24 +132,17 @@ struct MetDev {
     int HW;
 };
 
-__device__ __forceinline__ double met_wave_sum(double v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
 __global__ __launch_bounds__(EVAL_THREADS) void k_flow_metrics(const MetDev a)
 {
     __shared__ double sP[EVAL_WAVES * MET_NACC];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int n = blockIdx.y;
+    const unsigned blocks = gridDim.x;
     const float *pu = a.pr + (size_t)n * 2 * a.HW, *pv = pu + a.HW, *gu = a.gt + (size_t)n * 2 * a.HW, *gv = gu + a.HW;
     const float *va = a.valid ? a.valid + (size_t)n * a.HW : nullptr;
     double esum = 0.0;
     int nv = 0, n1 = 0, n3 = 0, n5 = 0, no = 0;
     // i < HW < 2^30 and the stride is at most MET_MAX_BLOCKS * EVAL_THREADS = 2^17, so the last increment cannot wrap
-    for (unsigned i = blockIdx.x * EVAL_THREADS + threadIdx.x; i < (unsigned)a.HW; i += gridDim.x * EVAL_THREADS) {
+    for (unsigned i = blockIdx.x * EVAL_THREADS + threadIdx.x; i < (unsigned)a.HW; i += blocks * EVAL_THREADS) {
         if (va && !(va[i] >= 0.5f)) continue;
         const float tu = gu[i], tv = gv[i];
         const float d0 = pu[i] - tu, d1 = pv[i] - tv;
@@ -158,18 +152,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_flow_metrics(const MetDev a)
         no += epe > 3.0f && epe / mag > 0.05f;
     }
     const double part[MET_NACC] = {esum, (double)nv, (double)n1, (double)n3, (double)n5, (double)no};
-#pragma unroll
-    for (int q = 0; q < MET_NACC; ++q) {
-        const double v = met_wave_sum(part[q]);
-        if (lane == 0) sP[wave * MET_NACC + q] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < MET_NACC) {
-        double v = sP[threadIdx.x];
-#pragma unroll
-        for (int q = 1; q < EVAL_WAVES; ++q) v += sP[q * MET_NACC + threadIdx.x];
-        a.partials[((size_t)n * gridDim.x + blockIdx.x) * MET_NACC + threadIdx.x] = v;
-    }
+    mpf_block_sums<EVAL_WAVES>(part, MET_NACC, sP, a.partials + ((size_t)n * blocks + blockIdx.x) * MET_NACC);
 }
 
 // one block per frame: its blocks' partials in a fixed order
@@ -181,12 +164,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_flow_metrics_finish(const MetD
     for (int q = 0; q < MET_NACC; ++q) {
         double v = 0.0;
         for (int b = threadIdx.x; b < blocks; b += EVAL_THREADS) v += part[(size_t)b * MET_NACC + q];
-        sR[threadIdx.x] = v;
-        __syncthreads();
-        for (int m = EVAL_THREADS / 2; m >= 1; m >>= 1) {
-            if ((int)threadIdx.x < m) sR[threadIdx.x] += sR[threadIdx.x + m];
-            __syncthreads();
-        }
+        mpf_block_tree_sum<EVAL_THREADS>(v, sR);
         if (threadIdx.x == 0) a.metrics[(size_t)n * MET_NACC + q] = sR[0];
         __syncthreads();
     }

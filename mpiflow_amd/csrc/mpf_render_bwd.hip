@@ -25,6 +25,7 @@
 // partials in block order in double (mpf_plane_sum_*): two runs give the same bits.
 #include "mpf_common.h"
 #include "mpf_math.h"
+#include "mpf_reduce.h"
 #include "mpf_render_geom.h"
 
 // ---- plane_volume_rendering / _flow ----------------------------------------------------------------------------------------------------
@@ -257,12 +258,12 @@ MPF_DEV float mpf_bwd_transparency(const float *__restrict__ sigma_plane, const 
 }
 
 // ---- per-plane sums over all pixels, without atomics ----------------------------------------------------------------------------------
-// At plane s every wave adds its 64 lanes (xor butterfly: EVERY lane must be there, so callers keep threads past the image alive with v = 0) and
+// At plane s every wave adds its 64 lanes (mpf_wave_sum: every lane must be there, so callers keep threads past the image alive with v = 0) and
 // lane 0 parks the sum in the LDS slot [wave][s]; after the plane loop the workgroup adds its wave slots in wave order into partial[block][s];
 // k_plane_sum_final adds the partials in block order, in double.  Every order is fixed: two runs give the same bits.
 MPF_DEV void mpf_plane_sum_push(float v, int s, int S, float *__restrict__ lds)
 {
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    v = mpf_wave_sum(v);
     if ((threadIdx.x & 63u) == 0) lds[(threadIdx.x >> 6) * S + s] = v;
 }
 

@@ -34,6 +34,7 @@
 //                          fp64 in row order, the 32 lanes fold in a fixed butterfly: no atomics, no workspace, bit-identical from run to run.
 #include "mpf_common.h"
 #include "mpf_convex.h"          // up_neighbourhood, up_convex: shared with the cropped upsampling of mpf_raft_eval.hip
+#include "mpf_reduce.h"
 #include "mpf_upflow8.h"
 
 #define UP_THREADS 256
@@ -61,13 +62,6 @@ struct UpDev {
     int N, H, W, HW, tiles;
     float max_flow;
 };
-
-__device__ __forceinline__ double up_wave_sum(double v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
 
 template <int MODE>
 __global__ __launch_bounds__(UP_THREADS) void k_upsample(const UpDev a)
@@ -190,19 +184,8 @@ __global__ __launch_bounds__(UP_THREADS) void k_upsample(const UpDev a)
         }
     }
     if (MODE == UP_LOSS) {
-        double part[UP_NPART] = {S, esum, (double)n1, (double)n3, (double)n5, (double)nv};
-        const int nq = a.metrics ? UP_NPART : 1;
-        for (int q = 0; q < nq; ++q) {
-            const double v = up_wave_sum(part[q]);
-            if (lane == 0) sP[wave * UP_NPART + q] = v;
-        }
-        __syncthreads();
-        if ((int)threadIdx.x < nq) {
-            double v = sP[threadIdx.x];
-#pragma unroll
-            for (int q = 1; q < UP_WAVES; ++q) v += sP[q * UP_NPART + threadIdx.x];
-            a.partials[(long long)blockIdx.x * UP_NPART + threadIdx.x] = v;
-        }
+        const double part[UP_NPART] = {S, esum, (double)n1, (double)n3, (double)n5, (double)nv};
+        mpf_block_sums<UP_WAVES>(part, a.metrics ? UP_NPART : 1, sP, a.partials + (long long)blockIdx.x * UP_NPART);
     }
 }
 
@@ -230,12 +213,7 @@ __global__ __launch_bounds__(UP_THREADS) void k_upsample_finish(const UpDev a, i
     for (int q = 0; q < nq; ++q) {
         double v = 0.0;
         for (int b = threadIdx.x; b < blocks; b += UP_THREADS) v += a.partials[(long long)b * UP_NPART + q];
-        sR[threadIdx.x] = v;
-        __syncthreads();
-        for (int m = UP_THREADS / 2; m >= 1; m >>= 1) {
-            if ((int)threadIdx.x < m) sR[threadIdx.x] += sR[threadIdx.x + m];
-            __syncthreads();
-        }
+        mpf_block_tree_sum<UP_THREADS>(v, sR);
         if (threadIdx.x == 0) {
             if (q == 0)
                 a.term[0] = (float)(sR[0] / ((double)a.N * 128.0 * (double)a.HW));
@@ -255,7 +233,6 @@ struct Up8Geo {
 __global__ __launch_bounds__(UP_THREADS) void k_up8_loss(const UpDev a, const Up8Geo q)
 {
     __shared__ double sP[UP_WAVES * UP_NPART];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int H = a.H, W = a.W, H8 = 8 * H, W8 = 8 * W;
     const unsigned per_row = (unsigned)(2 * W);
     const size_t plane = (size_t)H8 * W8;
@@ -294,19 +271,8 @@ __global__ __launch_bounds__(UP_THREADS) void k_up8_loss(const UpDev a, const Up
             }
         }
     }
-    double part[UP_NPART] = {S, esum, (double)n1, (double)n3, (double)n5, (double)nv};
-    const int nq = a.metrics ? UP_NPART : 1;
-    for (int k = 0; k < nq; ++k) {
-        const double v = up_wave_sum(part[k]);
-        if (lane == 0) sP[wave * UP_NPART + k] = v;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < nq) {
-        double v = sP[threadIdx.x];
-#pragma unroll
-        for (int k = 1; k < UP_WAVES; ++k) v += sP[k * UP_NPART + threadIdx.x];
-        a.partials[(size_t)blockIdx.x * UP_NPART + threadIdx.x] = v;
-    }
+    const double part[UP_NPART] = {S, esum, (double)n1, (double)n3, (double)n5, (double)nv};
+    mpf_block_sums<UP_WAVES>(part, a.metrics ? UP_NPART : 1, sP, a.partials + (size_t)blockIdx.x * UP_NPART);
 }
 
 __global__ __launch_bounds__(UP_THREADS) void k_up8_loss_bwd(const UpDev a, const Up8Geo q)
