@@ -88,6 +88,10 @@ def parse(argv=None):
                    help="windows of the sparse bilateral filter (3d-photo-inpainting's depth-edge sharpening, the call the reference keeps commented "
                         "out in disparity_to_tensor), one iteration per window, e.g. 5,5; run on the GPU on every disparity at file resolution before "
                         "the input stage.  Default: off (the reference's behaviour)")
+    p.add_argument("--adjust-planes", action="store_true",
+                   help="move the planes per image with the checkpoint's plane-adjustment network (model/PAN.py; the reference's forward has the call "
+                        "commented out and renders on fixed planes, the default here).  --mpi-from model only.  An image for which the network "
+                        "puts a plane at a disparity of 0 or below is not rendered and is listed in skipped.txt")
     p.add_argument("--resume", action="store_true", help="skip images whose outputs (all --repeat pairs) already exist; the RNG schedule is unaffected")
     p.add_argument("--gpus", type=int, default=0,
                    help="GPUs of this node to shard the images over, one process per GPU (the reference's model: scripts/gen_train_kitti15_v2.sh "
@@ -142,6 +146,8 @@ def self_launch(opt, argv):
 def main(argv=None):
     t_main = time.perf_counter()
     opt = parse(argv)
+    if opt.adjust_planes and opt.mpi_from != "model":
+        raise SystemExit("gen_3dphoto_dynamic: --adjust-planes runs the checkpoint's plane-adjustment network: it goes with --mpi-from model")
     if opt.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(opt, argv)
     if opt.model_engine == "torch" or os.environ.get("MPIFLOW_ENCODER") == "torch":
@@ -207,7 +213,7 @@ def main(argv=None):
             raise SystemExit("gen_3dphoto_dynamic: checkpoint %r not found.  The reference always runs the AdaMPI network from --ckpt_path "
                              "(gen_3dphoto_dynamic_v2.py:52-60); pass the checkpoint, or --ckpt_path random:SEED, or choose another "
                              "producer explicitly with --mpi-from npz|disparity." % opt.ckpt_path)
-        model = producer.load_model(opt.ckpt_path, opt.width, opt.height, opt.planes, dev)
+        model = producer.load_model(opt.ckpt_path, opt.width, opt.height, opt.planes, dev, adjust_planes=opt.adjust_planes)
         opt.planes = model.num_planes
     elif opt.mpi_from == "disparity" and rank == 0:
         print("WARNING: --mpi-from disparity is a stand-in producer (hard depth assignment), not the reference's AdaMPI network", file=sys.stderr)

@@ -51,7 +51,8 @@ extern "C" {
                              with MpfCannyArgs and the four mpf_stage2_* calls with MpfStage2Args, and now mpf_sparse_bilateral, mpf_sparse_bilateral_workspace
                              and mpf_sparse_bilateral_rank with MpfBilateralArgs, and now mpf_gather_pxpy, mpf_gather_pxpy_bwd, mpf_sample_pdf,
                              mpf_disp_consistency, its _bwd and _workspace calls with MpfGatherPxpyArgs / MpfSamplePdfArgs / MpfDispConsistencyArgs, and now mpf_flow_warp,
-                             mpf_flow_warp_bwd and mpf_flow_warp_workspace with MpfFlowWarpArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
+                             mpf_flow_warp_bwd and mpf_flow_warp_workspace with MpfFlowWarpArgs, and now mpf_pan_block1 and mpf_pan_block1_workspace with
+                             MpfPanArgs) only ADD symbols: the number, which tests/test_capi.py pins, stays 601 */
 
 /* d_params layout (floats):
  *   [0..8]   K_src^-1 (3x3 row-major)            [9..20]  G_tgt_src rows 0..2 (3x4 row-major: R | t)
@@ -1086,6 +1087,39 @@ typedef struct MpfFlowWarpArgs {
 size_t mpf_flow_warp_workspace(int B, int C, int H, int W, int whole);    /* 0 where none is needed, and for a shape the calls refuse */
 int mpf_flow_warp(const MpfFlowWarpArgs *a, void *stream);
 int mpf_flow_warp_bwd(const MpfFlowWarpArgs *a, void *stream);
+
+/* The first residual block of AdaMPI's plane-adjustment network (model/PAN.py:18-46, block 0 of its DownsizeEncoder) over the S plane-images of
+ * each of B images, in eval mode, with its 2 x 2 average pool; INTEGRATION.md section 23 states it (tests/pan_restated.py restates it in float64).
+ * The S inputs x_s = cat(rgb_low, disp_low, d_s) of an image differ only in the constant channel d_s = plane_disp[b,s], and conv1 / conv3 are
+ * affine in it, so the launch splits in two:
+ *   prologue, once per image   A1[o,y,x] = b1[o] + sum over the four image channels and the in-frame taps of w1[o,c,tap] * x[c,y+dy,x+dx]
+ *                              B1[o,y,x] = sum over the in-frame taps of w1[o,4,tap]    (zero padding: it differs from the inner value only on the border)
+ *                              A3[o,y,x] = bias3[o] + sum over the four image channels of w3[o,c] * x[c,y,x]
+ *   per plane, fused           m = bn_scale * relu(A1 + d_s * B1) + bn_shift inside the frame, 0 outside it (conv2 pads ITS input with zeros);
+ *                              v = relu(b2 + conv2(m) + A3 + d_s * w3[o,4]);  out = the mean of v over 2 x 2, h / 2 x w / 2 pixels (floor: an odd
+ *                              last row / column is dropped, as avg_pool2d drops it).
+ * bn_scale = weight / sqrt(running_var + eps) and bn_shift = bias - running_mean * bn_scale are folded by the caller.  All tensors f32, contiguous,
+ * 4-byte aligned; sums in f32 with fused multiply-adds; no atomics: identical bytes on every run.  plane_disp is read on the device.  Everything is
+ * validated before anything is launched (MPF_ERR_BAD_ARGUMENT): a NULL block or pointer, a pointer that is not 4-byte aligned, h or w below 2,
+ * B or S below 1, a workspace that is too small, B * S * 8 * (h / 2) * (w / 2) or B * 8 * h * w of 2^31 or more, more than 65535 row tiles or
+ * (image, plane group) slices.  Nothing synchronises with the host. */
+#define MPF_PAN_C 8                  /* channels of the block: conv1 5 -> 8, conv2 8 -> 8, conv3 5 -> 8 */
+#define MPF_PAN_PLANES_PER_GROUP 4   /* planes one workgroup walks with the tile's A1 / B1 / A3 in registers */
+typedef struct MpfPanArgs {
+    const float *rgb_low;            /* [B,3,h,w] */
+    const float *disp_low;           /* [B,1,h,w] */
+    const float *plane_disp;         /* [B,S] on the device */
+    const float *w1, *b1;            /* conv1 [8,5,3,3], [8] */
+    const float *bn_scale, *bn_shift;/* [8], [8]: the eval-mode BatchNorm folded */
+    const float *w2, *b2;            /* conv2 [8,8,3,3], [8] */
+    const float *w3, *b3;            /* conv3 [8,5,1,1], [8] */
+    float *out;                      /* [B*S,8,h/2,w/2] */
+    void *workspace;                 /* mpf_pan_block1_workspace(B, h, w) bytes: A1 [B,8,h,w], A3 [B,8,h,w], B1 [8,h,w]; contents irrelevant before the call */
+    size_t workspace_bytes;
+    int B, S, h, w;
+} MpfPanArgs;
+size_t mpf_pan_block1_workspace(int B, int h, int w);                     /* 0 for a shape the call refuses */
+int mpf_pan_block1(const MpfPanArgs *a, void *stream);
 
 /* The optimizer tail of RAFT/train.py (train.py:178-181: clip_grad_norm_, AdamW.step) over a whole parameter set, as one multi-tensor path:
  * the global gradient norm, the clip coefficient and torch's single-tensor AdamW update, without host synchronisation.  All tensors f32.

@@ -262,6 +262,17 @@ class MpfFlowWarpArgs(ctypes.Structure):
                 ("whole", c_i)]
 
 
+PAN_C = 8                                   # MPF_PAN_C
+PAN_PLANES_PER_GROUP = 4                    # MPF_PAN_PLANES_PER_GROUP
+
+
+class MpfPanArgs(ctypes.Structure):
+    """struct MpfPanArgs of include/mpiflow_hip.h: the first residual block of the plane-adjustment network over the S plane-images, pooled."""
+    _fields_ = [("rgb_low", c_p), ("disp_low", c_p), ("plane_disp", c_p), ("w1", c_p), ("b1", c_p), ("bn_scale", c_p), ("bn_shift", c_p), ("w2", c_p),
+                ("b2", c_p), ("w3", c_p), ("b3", c_p), ("out", c_p), ("workspace", c_p), ("workspace_bytes", c_sz), ("B", c_i), ("S", c_i), ("h", c_i),
+                ("w", c_i)]
+
+
 WARM_MAX_HW = 65536             # MPF_WARM_MAX_HW
 WARM_MAX_NHW = 1 << 22          # MPF_WARM_MAX_NHW
 
@@ -384,6 +395,8 @@ SIGNATURES = {
     "mpf_flow_warp_workspace": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
     "mpf_flow_warp": (c_i, [ctypes.POINTER(MpfFlowWarpArgs), c_p]),
     "mpf_flow_warp_bwd": (c_i, [ctypes.POINTER(MpfFlowWarpArgs), c_p]),
+    "mpf_pan_block1_workspace": (c_sz, [c_i, c_i, c_i]),
+    "mpf_pan_block1": (c_i, [ctypes.POINTER(MpfPanArgs), c_p]),
     "mpf_adamw_workspace": (c_sz, [ctypes.POINTER(MpfOptTensor), c_i]),
     "mpf_grad_norm": (c_i, [ctypes.POINTER(MpfAdamWArgs), c_p]),
     "mpf_adamw_clipped": (c_i, [ctypes.POINTER(MpfAdamWArgs), c_p]),

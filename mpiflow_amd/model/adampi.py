@@ -5,9 +5,13 @@ Architecture and parameter names follow the reference so its checkpoints load wi
   RGBD ResNet-18 encoder  model/CPN/encoder.py:20-101 (torchvision ResNet layout: conv1, bn1, layer1-4, fc)
   FeatMaskNetwork         model/CPN/unet.py:18-69
   DepthDecoder            model/CPN/decoder.py:74-174 (ModuleDict keys are '-'.join(str(tuple)), :75-77)
-  DepthPredictionNetwork  model/PAN.py:80-109         present for checkpoint compatibility; bypassed in forward, as in the
-                                                      reference (model/AdaMPI.py:70-71): plane disparities are always
-                                                      linspace(1, 0.001, S+2)[1:-1]
+  DepthPredictionNetwork  model/PAN.py:80-109         the plane-adjustment network.  The reference's forward has its call commented out
+                                                      (model/AdaMPI.py:70-71) and renders on linspace(1, 0.001, S+2)[1:-1]; so does
+                                                      MPIPredictor by default.  MPIPredictor(adjust_planes=True) runs that commented line:
+                                                      render_disp = dpn(fixed planes, rgb_low, disp_low).  In eval mode, on the GPU, in
+                                                      float32 and without a gradient its first residual block, where its cost sits, runs as
+                                                      the fused HIP kernel ops.pan_block1 (csrc/mpf_pan.hip); blocks 2-5, the attention, the
+                                                      embedding and to_disp are torch's.  INTEGRATION.md section 23.
 """
 import numpy as np
 import torch
@@ -205,7 +209,7 @@ class DepthDecoder(nn.Module):
         return torch.cat((rgb, sigma), dim=2)
 
 
-# ---- plane-adjust network (kept for checkpoint compatibility; bypassed) ---------------------------------------------
+# ---- plane-adjustment network (MPIPredictor(adjust_planes=True); off by default, as the reference's forward leaves it) ----------
 
 class _ResBlock(nn.Module):
     def __init__(self, c_in, c_out, c_hid):
@@ -230,8 +234,9 @@ class _DownsizeEncoder(nn.Module):
             blocks.append(_ResBlock(a, b, b))
         self.res_blocks = nn.ModuleList(blocks)
 
-    def forward(self, x):
-        for blk in self.res_blocks:
+    def forward(self, x, start=0):
+        """start: the first block to run (1: x is already the pooled output of block 0)"""
+        for blk in self.res_blocks[start:]:
             x = F.avg_pool2d(blk(x), 2)
         return x
 
@@ -269,24 +274,71 @@ class DepthPredictionNetwork(nn.Module):
         self.self_attention = _MHSA(4, 128, 32, 128)
         self.embed = nn.Sequential(nn.Linear(128, 32), nn.ReLU())
         self.to_disp = _LinearSigmoid(32)
+        self._folded = None                                 # (key, scale, shift): block 0's eval-mode BatchNorm folded for the fused kernel
+
+    def fused_block1_applies(self, init_disp, rgb_low, disp_low):
+        """The fused first block is the eval-mode function in float32 on the GPU and carries no gradient: anything else is torch's."""
+        tensors = (init_disp, rgb_low, disp_low)
+        if self.training or not all(t.is_cuda and t.dtype == torch.float32 for t in tensors):
+            return False
+        params = list(self.context_encoder.res_blocks[0].parameters())
+        if not all(p.is_cuda and p.dtype == torch.float32 for p in params):
+            return False
+        return not (torch.is_grad_enabled() and any(t.requires_grad for t in list(tensors) + list(self.parameters())))
+
+    def _folded_bn(self, bn):
+        """scale = weight / sqrt(running_var + eps), shift = bias - running_mean * scale, on the device; refolded when a tensor was written or moved"""
+        src = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+        key = tuple((t.data_ptr(), t._version) for t in src) + (bn.eps,)
+        if self._folded is None or self._folded[0] != key:
+            with torch.no_grad():
+                scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
+                self._folded = (key, scale.contiguous(), (bn.bias - bn.running_mean * scale).contiguous())
+        return self._folded[1], self._folded[2]
+
+    def block1(self, init_disp, rgb_low, disp_low, fused):
+        """The first residual block and its pool over the B * S plane-images -> [B*S,8,h//2,w//2].  fused: ops.pan_block1, which never forms the
+        plane-images; else the torch modules on cat(rgb_low, disp_low, d_s), as the reference runs them."""
+        B, S = init_disp.shape
+        h, w = rgb_low.shape[-2:]
+        blk = self.context_encoder.res_blocks[0]
+        if fused:
+            from .. import ops
+            scale, shift = self._folded_bn(blk.bn)
+            return ops.pan_block1(rgb_low.contiguous(), disp_low.contiguous(), init_disp.contiguous(), blk.conv1.weight, blk.conv1.bias, scale, shift,
+                                  blk.conv2.weight, blk.conv2.bias, blk.conv3.weight, blk.conv3.bias)
+        x = torch.cat([rgb_low[:, None].expand(B, S, 3, h, w), disp_low[:, None].expand(B, S, 1, h, w),
+                       init_disp[:, :, None, None, None].expand(B, S, 1, h, w)], dim=2).reshape(B * S, 5, h, w)
+        return F.avg_pool2d(blk(x), 2)
 
     def forward(self, init_disp, rgb_low, disp_low):
         B, S = init_disp.shape
-        h, w = rgb_low.shape[-2:]
-        x = torch.cat([rgb_low[:, None].expand(B, S, 3, h, w), disp_low[:, None].expand(B, S, 1, h, w),
-                       init_disp[:, :, None, None, None].expand(B, S, 1, h, w)], dim=2).reshape(B * S, 5, h, w)
-        ctx = F.adaptive_avg_pool2d(self.context_encoder(x), (1, 1)).reshape(B, S, -1)
+        fused = self.fused_block1_applies(init_disp, rgb_low, disp_low)
+        x = self.block1(init_disp, rgb_low, disp_low, fused)
+        # Blocks 2-5 are torch's convolutions.  MIOpen's default choice of algorithm for them differs from call to call in one process, by up to
+        # 2e-6 of the planes; its deterministic algorithms do not (HipPredictor asks for them for the same reason).  The fast path asks for them,
+        # so that an image gets the same planes every time; the torch path is left as it was.
+        det = torch.backends.cudnn.deterministic
+        torch.backends.cudnn.deterministic = det or fused
+        try:
+            ctx = F.adaptive_avg_pool2d(self.context_encoder(x, start=1), (1, 1)).reshape(B, S, -1)
+        finally:
+            torch.backends.cudnn.deterministic = det
         return self.to_disp(self.embed(self.self_attention(ctx)), init_disp)
 
 
 # ---- top level ----------------------------------------------------------------------------------------------------------
 
 class MPIPredictor(nn.Module):
-    """(src_imgs [B,3,H,W], src_depths [B,1,H,W]) -> (mpi [B,S,4,H,W], plane disparities [B,S])   model/AdaMPI.py:55-78"""
+    """(src_imgs [B,3,H,W], src_depths [B,1,H,W]) -> (mpi [B,S,4,H,W], plane disparities [B,S])   model/AdaMPI.py:55-78
 
-    def __init__(self, width=384, height=256, num_planes=64):
+    adjust_planes: False (default) renders on the fixed planes, as the reference's forward does; True moves them with the plane-adjustment network
+    (the reference's commented line, model/AdaMPI.py:70).  Its output is init + linear(...) / S: unbounded and not re-sorted, handed on as it is."""
+
+    def __init__(self, width=384, height=256, num_planes=64, adjust_planes=False):
         super().__init__()
         self.num_planes = num_planes
+        self.adjust_planes = bool(adjust_planes)
         self.far, self.near = 0.001, 1
         self.low_res_size = (int(height / 4), int(width / 4))
         self.encoder = ResnetEncoder()
@@ -298,8 +350,17 @@ class MPIPredictor(nn.Module):
         d = torch.linspace(self.near, self.far, self.num_planes + 2)[1:-1]
         return d.to(like.dtype).to(like.device).unsqueeze(0).repeat(like.shape[0], 1)
 
-    def forward(self, src_imgs, src_depths, raw=False):
+    def render_disparities(self, src_imgs, src_depths):
+        """The planes the image renders on [B,S]: the fixed ones, or with adjust_planes the plane-adjustment network's (model/AdaMPI.py:60-71)"""
         disp = self.plane_disparities(src_imgs)
+        if not self.adjust_planes:
+            return disp
+        rgb_low = F.interpolate(src_imgs, size=self.low_res_size, mode="bilinear", align_corners=True)
+        disp_low = F.interpolate(src_depths, size=self.low_res_size, mode="bilinear", align_corners=True)
+        return self.dpn(disp, rgb_low, disp_low)
+
+    def forward(self, src_imgs, src_depths, raw=False):
+        disp = self.render_disparities(src_imgs, src_depths)
         feature_mask = self.fmn(src_imgs, src_depths, disp)
         feats = self.encoder(src_imgs, src_depths)
         out = self.decoder(feats, feature_mask, raw=raw)
@@ -325,9 +386,9 @@ class MPIPredictor(nn.Module):
         return self
 
     @classmethod
-    def from_checkpoint(cls, path, width, height, map_location="cpu"):
+    def from_checkpoint(cls, path, width, height, map_location="cpu", adjust_planes=False):
         """Load a reference checkpoint: {'num_planes': S, 'weight': state_dict}   (gen_3dphoto_dynamic_v2.py:52-58)"""
         ckpt = torch.load(path, map_location=map_location)
-        model = cls(width=width, height=height, num_planes=ckpt["num_planes"])
+        model = cls(width=width, height=height, num_planes=ckpt["num_planes"], adjust_planes=adjust_planes)
         model.load_state_dict(ckpt["weight"])
         return model.eval()

@@ -20,6 +20,7 @@ import os
 import torch
 
 from .. import _lib
+from .planes import PerCallPlanes
 
 LD_FMN_INPUT, LD_DIRECT, LD_BILINEAR_CAT, LD_NEAREST_PLANE, LD_FMN_SYNTH, LD_BILINEAR_SYNTH, LD_NEAREST_PHASE = 0, 1, 2, 3, 4, 5, 6
 EP_AFFINE_RELU, EP_AFFINE_RELU_F32, EP_GATED_ELU, EP_GATED_PLANAR_F32, EP_AFFINE_F32_NHWC, EP_GATED_PLANAR_F32_PAIRED, EP_GATED_ELU_PAIRED = 0, 1, 2, 3, 4, 5, 6
@@ -665,7 +666,7 @@ def pad16(c):
     return (int(c) + 15) // 16 * 16
 
 
-class HipPredictor:
+class HipPredictor(PerCallPlanes):
     """MPIPredictor.forward(raw=True) (model/AdaMPI.py:55-78) for one image with the per-plane networks on the HIP engine.
 
     encoder: "hip" (default; env MPIFLOW_ENCODER) = EncoderEngine, the single-image part as fp32 HIP kernels (0.64 ms alone, forward 7.8 ms);
@@ -698,12 +699,12 @@ class HipPredictor:
         # constants the torch parts would otherwise copy from the host on every call (not allowed while capturing a graph)
         model.encoder.img_mean = model.encoder.img_mean.to(dev)
         model.encoder.img_std = model.encoder.img_std.to(dev)
-        self._plane_disp = model.plane_disparities(torch.zeros(1, device=dev))[0].contiguous()
+        self._init_planes(model, dev)      # _plane_disp: the fixed planes; _planes: the buffer every forward (and a captured graph) reads
 
     @torch.no_grad()
     def _forward(self, src_imgs, src_depths):
         m = self.model
-        disp = self._plane_disp
+        disp = self._planes
         # the single-image part (encoder, bottleneck: 28 small launches) runs on a side stream underneath the feature-mask
         # network, which fills the GPU on its own; the decoder joins the two
         main = torch.cuda.current_stream()
@@ -756,10 +757,13 @@ class HipPredictor:
         return rows, dict(flops=sum(r["flops"] for r in rows), bytes=sum(r["bytes"] for r in rows))
 
     @torch.no_grad()
-    def __call__(self, src_imgs, src_depths):
-        """(image [1,3,H,W], disparity [1,1,H,W]) -> (raw [S,4,H,W] fp32, cum_mask [S,H,W] fp32, plane disparities [S])"""
+    def __call__(self, src_imgs, src_depths, plane_disp=None):
+        """(image [1,3,H,W], disparity [1,1,H,W]) -> (raw [S,4,H,W] fp32, cum_mask [S,H,W] fp32, plane disparities [S]: the planes used)
+        plane_disp: None = the fixed planes; a device [S] float32 tensor = this image's planes, copied into the buffer the (captured) forward
+        reads - no re-capture."""
         if src_imgs.shape[0] != 1:
             raise ValueError("HipPredictor runs one image at a time (the S planes are the batch)")
+        self._set_planes(plane_disp)
         if not self.graph:
             return self._forward(src_imgs, src_depths)
         key = (tuple(src_imgs.shape), src_imgs.device.index)

@@ -20,6 +20,7 @@ import os
 import torch
 
 from .. import _lib
+from .planes import PerCallPlanes
 
 EP_AFFINE, EP_AFFINE_MAP, EP_GATED, EP_GATED_PLANAR = 0, 1, 2, 3
 DTYPE_CODE = {torch.float32: 0, torch.float64: 1}
@@ -307,7 +308,7 @@ def _stream(dev):
     return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
-class PrecisePredictor:
+class PrecisePredictor(PerCallPlanes):
     """MPIPredictor.forward(raw=True) (model/AdaMPI.py:55-78) for one image, every layer on mpf_pconv in `dtype` (torch.float32 or torch.float64).
 
     __call__(image [1,3,H,W], disparity [1,1,H,W]) -> (raw [S,4,H,W], cum_mask [S,H,W], plane disparities [S]) - the hand-off
@@ -372,7 +373,7 @@ class PrecisePredictor:
             else:
                 self.up1[i] = G(b1.gated_conv, b1.bn, [(dec[0], dec[0])], up=1, name="up1_0")
         self.disp0 = G(d.convs[key("dispconv", 0)], None, [(dec[0], dec[0])], planar=True, name="disp0")
-        self._plane_disp = model.plane_disparities(torch.zeros(1, device=dev))[0].contiguous()
+        self._init_planes(model, dev)      # _plane_disp: the fixed planes; _planes: the buffer every forward reads
         self._side = torch.cuda.Stream(device=dev)
         self.debug = None                                              # set to a dict to keep intermediate tensors (tests)
 
@@ -476,9 +477,11 @@ class PrecisePredictor:
         return self.disp0(S, h, w, x)
 
     @torch.no_grad()
-    def __call__(self, src_imgs, src_depths):
+    def __call__(self, src_imgs, src_depths, plane_disp=None):
+        """plane_disp: None = the fixed planes; a device [S] float32 tensor = this image's planes (HipPredictor.__call__)"""
         if src_imgs.shape[0] != 1:
             raise ValueError("PrecisePredictor runs one image at a time (the S planes are the batch)")
+        self._set_planes(plane_disp)
         H, W = src_imgs.shape[-2:]
         for n in (H, W):
             # five x2 scales down to 1/32, then the bottleneck's two stride-2 pools and two x2 up-samplings must return to that size - the
@@ -488,7 +491,7 @@ class PrecisePredictor:
                 raise ValueError("H and W must be multiples of 32 whose 1/32 size survives two stride-2 pools and two x2 up-samplings, got %d" % n)
         with torch.cuda.device(self.dev):
             img, dsp = src_imgs[0].float().contiguous(), src_depths[0, 0].float().contiguous()
-            pd = self._plane_disp
+            pd = self._planes
             # the single-image part (ResNet-18 + bottleneck: ~30 launches of a few dozen workgroups) runs beside the S-plane UNet on a second stream
             main = torch.cuda.current_stream(self.dev)
             self._side.wait_stream(main)

@@ -219,12 +219,13 @@ class OnlinePairs:
     mix: shuffle-buffer size in pairs (0 = off).  prefetch: batches enqueued ahead of the consumer.  rank / world_size: default from
     torch.distributed or RANK / WORLD_SIZE.  fill_threads: host threads of fill="builtin" (default: default_fill_threads()).
     disp_filter: None = none, or the windows of the sparse bilateral filter, such as (5, 5), run on every disparity before the input stage
-    (the CLI's --disp-filter)."""
+    (the CLI's --disp-filter).  adjust_planes: False = the fixed planes; True = the checkpoint's plane-adjustment network moves them per image (the
+    CLI's --adjust-planes; mpi_from="model" only); an image for which it puts a plane at a disparity of 0 or below is skipped (`skipped`)."""
 
     def __init__(self, base, batch_size=8, crop=(288, 960), width=1280, height=384, seed=114514, ext_cz=0.15, pairs_per_image=5, poses="v2",
                  mpi_from="model", ckpt_path=None, model_dtype="auto", fill="auto", augment=dict(min_scale=-0.2, max_scale=0.5, do_flip=True),
                  shuffle=True, mix=32, prefetch=2, rank=None, world_size=None, device=None, planes=64, fill_threads=None, photometric=None,
-                 sparse=None, disp_filter=None):
+                 sparse=None, disp_filter=None, adjust_planes=False):
         if torch.utils.data.get_worker_info() is not None:
             raise RuntimeError("OnlinePairs renders on the GPU in the training process: construct it there, not inside a DataLoader worker")
         if mpi_from not in ("model", "npz", "disparity"):
@@ -240,6 +241,9 @@ class OnlinePairs:
         self.sparse = sparse_config(sparse, self.augment)
         self.photometric = photometric_config(photometric, sparse=self.sparse is not None)
         self.disp_filter = producer.parse_disp_filter(disp_filter)
+        self.adjust_planes = bool(adjust_planes)
+        if self.adjust_planes and mpi_from != "model":
+            raise ValueError("adjust_planes runs the checkpoint's plane-adjustment network: it goes with mpi_from='model'")
         if rank is None or world_size is None:
             import torch.distributed as dist
             if dist.is_available() and dist.is_initialized():
@@ -308,7 +312,7 @@ class OnlinePairs:
                     raise ValueError("mpi_from='model' needs ckpt_path (a checkpoint, or random:SEED)")
                 self.stream.wait_stream(torch.cuda.current_stream(dev))
                 with torch.cuda.stream(self.stream):
-                    model = producer.load_model(ckpt_path, self.W, self.H, self.planes, dev)
+                    model = producer.load_model(ckpt_path, self.W, self.H, self.planes, dev, adjust_planes=self.adjust_planes)
                 self.planes = model.num_planes
             self.lane = producer.Lane(dev, self.H, self.W, self.planes, model, model_dtype, streams=(self.stream, self.tail), disp_filter=self.disp_filter)
             if model is not None and model_dtype in ("auto", "fp16"):

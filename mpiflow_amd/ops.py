@@ -2029,6 +2029,49 @@ def flow_warp_backward(x, flow, g_out, mode, want_x=True, want_flow=True, grad_x
     return (grad_x if want_x else None), grad_flow
 
 
+@_on_device
+def pan_block1(rgb_low, disp_low, plane_disp, w1, b1, bn_scale, bn_shift, w2, b2, w3, b3, out=None):
+    """mpf_pan_block1: the first residual block of the plane-adjustment network (model/PAN.py:18-46) with its 2 x 2 average pool over the S
+    plane-images cat(rgb_low, disp_low, d_s) of each image, eval mode: conv1 and conv3 factorised into per-image maps built once, the rest fused per
+    plane.  rgb_low [B,3,h,w], disp_low [B,1,h,w], plane_disp [B,S] (read on the device); w1 [8,5,3,3], b1 [8], w2
+    [8,8,3,3], b2 [8], w3 [8,5,1,1], b3 [8] the block's parameters, bn_scale / bn_shift [8] its eval-mode BatchNorm folded.  -> out
+    [B*S,8,h//2,w//2].  float32, contiguous, on one GPU, or MpiFlowHipError before anything is launched.  Identical bytes on every run.  Asynchronous
+    on the current stream."""
+    who = "pan_block1"
+    C = _lib.PAN_C
+    rgb = check_tensor(rgb_low, "rgb_low", who, (None, 3, None, None), "[B,3,h,w]")
+    B, _, h, w = rgb.shape
+    checked = dict(rgb_low=rgb)
+    checked["disp_low"] = check_tensor(disp_low, "disp_low", who, (B, 1, h, w), "[B,1,h,w] with rgb_low's B, h, w = %d, %d, %d" % (B, h, w))
+    checked["plane_disp"] = pd = check_tensor(plane_disp, "plane_disp", who, (B, None), "[B,S] with rgb_low's B = %d" % B)
+    S = pd.shape[1]
+    for name, t, shape in (("w1", w1, (C, 5, 3, 3)), ("b1", b1, (C,)), ("bn_scale", bn_scale, (C,)), ("bn_shift", bn_shift, (C,)), ("w2", w2, (C, C, 3, 3)),
+                           ("b2", b2, (C,)), ("w3", w3, (C, 5, 1, 1)), ("b3", b3, (C,))):
+        checked[name] = check_tensor(t, name, who, shape)
+    if out is not None:
+        checked["out"] = check_tensor(out, "out", who, (B * S, C, h // 2, w // 2), "[B*S,8,h//2,w//2]")
+    if B < 1 or S < 1 or h < 2 or w < 2:
+        raise _lib.MpiFlowHipError("%s: at least one image and one plane, h and w at least 2 (got B, S, h, w = %d, %d, %d, %d)" % (who, B, S, h, w))
+    groups = (S + _lib.PAN_PLANES_PER_GROUP - 1) // _lib.PAN_PLANES_PER_GROUP
+    if B * S * C * (h // 2) * (w // 2) >= 1 << 31 or B * C * h * w >= 1 << 31 or B * groups > 65535 or (h // 2 + 3) // 4 > 65535:
+        raise _lib.MpiFlowHipError("%s: B * S * 8 * (h // 2) * (w // 2) and B * 8 * h * w below 2^31, at most 65535 (image, plane group) slices and row tiles "
+                                   "(got B, S, h, w = %d, %d, %d, %d)" % (who, B, S, h, w))
+    check_devices(who, checked)
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty((B * S, C, h // 2, w // 2), dtype=_f32, device=rgb.device)
+    need = int(lib.mpf_pan_block1_workspace(B, h, w))
+    ws = torch.empty(need, dtype=torch.uint8, device=rgb.device)
+    a = _lib.MpfPanArgs()
+    a.rgb_low, a.disp_low, a.plane_disp, a.out = rgb.data_ptr(), disp_low.data_ptr(), pd.data_ptr(), out.data_ptr()
+    a.w1, a.b1, a.bn_scale, a.bn_shift, a.w2, a.b2, a.w3, a.b3 = (t.data_ptr() for t in (w1, b1, bn_scale, bn_shift, w2, b2, w3, b3))
+    a.workspace, a.workspace_bytes = ws.data_ptr(), need
+    a.B, a.S, a.h, a.w = B, S, h, w
+    _lib.check(lib.mpf_pan_block1(ctypes.byref(a), _stream()), "mpf_pan_block1")
+    del ws                                                      # stream-ordered allocator: a later allocation on this stream queues behind the kernels
+    return out
+
+
 def _stage2_args(who, B, h, w, **tensors):
     """MpfStage2Args with the named fields set; every tensor already checked"""
     if B < 1 or h < 1 or w < 1 or B > 65535 or B * h * w > (1 << 28):

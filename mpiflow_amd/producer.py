@@ -47,17 +47,32 @@ def mpi_from_disparity(image_3HW, disp_HW, S):
     return mpi, planes
 
 
-def load_model(ckpt_path, W, H, planes, device):
+class PlaneRefused(ValueError):
+    """An image whose adjusted planes cannot be rendered: a plane with a disparity of 0 or below (or NaN) has no depth"""
+
+
+def check_planes(name, planes_host):
+    """planes_host [S] on the host, the plane-adjustment network's output for image `name`: unbounded, handed on as it is - and refused here,
+    before anything renders on it, where a plane has no depth"""
+    bad = ~(planes_host > 0)
+    if bool(bad.any()):
+        k = int(torch.nonzero(bad)[0])
+        raise PlaneRefused("image %s: plane %d of %d has disparity %g after plane adjustment; a plane needs a disparity above 0 to have a depth. "
+                           "The network's output is handed on as it is (not clamped, not re-sorted), so this image is not rendered"
+                           % (name, k, planes_host.numel(), float(planes_host[k])))
+
+
+def load_model(ckpt_path, W, H, planes, device, adjust_planes=False):
     """The MPIPredictor of a checkpoint (which carries its own num_planes) or of "random:SEED" (deterministic random weights, `planes` planes),
-    on `device`.  Leaves torch's global RNG as it was: module construction draws default initialisations from it."""
+    on `device`; adjust_planes: MPIPredictor's.  Leaves torch's global RNG as it was: module construction draws default initialisations from it."""
     from .model import MPIPredictor
     ckpt_path = str(ckpt_path)
     with torch.random.fork_rng(devices=[]):
         if ckpt_path.startswith("random:"):
-            return MPIPredictor(W, H, planes).randomize_(int(ckpt_path.split(":")[1])).eval().to(device)
+            return MPIPredictor(W, H, planes, adjust_planes=adjust_planes).randomize_(int(ckpt_path.split(":")[1])).eval().to(device)
         if not os.path.exists(ckpt_path):
             raise FileNotFoundError("checkpoint %r not found" % (ckpt_path,))
-        return MPIPredictor.from_checkpoint(ckpt_path, W, H).to(device)
+        return MPIPredictor.from_checkpoint(ckpt_path, W, H, adjust_planes=adjust_planes).to(device)
 
 
 def make_predictor(model, model_dtype):
@@ -107,7 +122,9 @@ class Lane:
     model_dtype: the HIP engine make_predictor builds for `model`; None runs `model` as torch modules under autocast `amp`.  lap(label): a
     context factory timing the stages (no-op by default).  streams: (render, tail) streams the caller created, default two new ones.
     disp_filter: None, or the windows of ops.sparse_bilateral_filter (such as (5, 5)), run on the uploaded disparity bytes at file
-    resolution before the input stage.  front() and pairs() enqueue on the current stream: call them inside torch.cuda.stream(lane.stream)."""
+    resolution before the input stage.  A model built with adjust_planes=True moves the planes per image: front() runs the plane-adjustment
+    network once, copies its S values to the host once (the renderer's homographies are built there), refuses an image with a plane at or
+    below 0 (PlaneRefused, before anything renders) and hands the same values to the engine and to the renderer.  front() and pairs() enqueue on the current stream: call them inside torch.cuda.stream(lane.stream)."""
 
     def __init__(self, device, H, W, planes, model=None, model_dtype=None, amp=None, lap=contextlib.nullcontext, streams=None, disp_filter=None):
         self.device, self.H, self.W, self.planes, self.K = device, H, W, planes, intrinsics(W, H)
@@ -121,6 +138,7 @@ class Lane:
             self.ns_ws = None                                     # fill "ns-hip": sized by its first use (ns_workspace)
             self.inputs = dict(image=torch.empty((3, H, W), device=device), disp=torch.empty((H, W), device=device))
             self.predictor = make_predictor(model, model_dtype) if model is not None and model_dtype is not None else None
+        self.adjust_planes = bool(getattr(model, "adjust_planes", False))
         self.tail_stream.wait_stream(self.stream)
 
     def ns_workspace(self, B):
@@ -151,12 +169,23 @@ class Lane:
             if npz is not None:
                 z = np.load(npz)
                 mpi, planes = torch.from_numpy(z["mpi"]).to(dev), torch.from_numpy(z["disparity"]).to(dev)
+            elif self.predictor is not None and self.adjust_planes:
+                with torch.no_grad():
+                    pd = self.model.render_disparities(image, disp)[0].float().contiguous()
+                # the image's one device-to-host copy of its S planes (256 bytes at S = 64): the host waits here for the upload and the
+                # plane-adjustment network, BEFORE the engine's forward is enqueued, so the wait does not include it
+                planes = pd.cpu()
+                check_planes(item.get("name", item.get("i")), planes)
+                mpi, cum_mask, _ = self.predictor(image, disp, plane_disp=pd)       # the engine reads the device values, the renderer the host's
             elif self.predictor is not None:
                 mpi, cum_mask, planes = self.predictor(image, disp)        # static buffers: consumed by blend() below
             elif self.model is not None:
                 with torch.no_grad(), torch.autocast("cuda", dtype=self.amp, enabled=self.amp is not None):      # :92-93
                     raw, cm, pd = self.model(image, disp, raw=True)
                 mpi, cum_mask, planes = raw[0].float().contiguous(), cm[0].float().contiguous(), pd[0].float()
+                if self.adjust_planes:                                     # the torch modules ran the network inside their forward: the same copy and check
+                    planes = planes.cpu()
+                    check_planes(item.get("name", item.get("i")), planes)
             else:
                 mpi, planes = mpi_from_disparity(image[0], disp[0, 0], self.planes)
             self.renderer.blend(mpi, image[0], self.K, planes, cum_mask=cum_mask)      # once per image; its pairs reuse it
